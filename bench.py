@@ -16,10 +16,17 @@ the jitter when timing starts; the rows are gathered inside the step.  N > 1: on
 OWN submap (weak scaling); the only exchange of the timed region is an all-gather of the optimised keyframe
 poses once per BA round (mapping.iters steps); the other shardings are exercised after it (`multi_gpu`).
 
-Besides the contract fields the line carries: `step_ms_stats` (min / median / p95 over >= 200 further steps),
-`kernels` (per-kernel roofline from event pairs on the launch stream), `frame` (MEASURED tracking+mapping ms/frame of a
-31-frame sequence with the reference's host sampling run ahead by producer threads, and with device sampling),
-`roofline`, `cpu_baseline`.
+A plain run sets up, warms up, times the K steps and prints the contract fields (`ms_per_step` = one timed step).  The K
+steps are hipGraph replays of pose_accum_step iterations; when they cannot be (--no-graph, --torch-pose, K not a multiple of
+pose_accum_step) they run eagerly, and a plain run then times them WITHOUT the per-kernel event pairs that the eager pass of
+`--full` records (so the two modes report slightly different eager `ms_per_step` for the same arguments).  With `--full` the
+line also carries: `step_ms_stats` (min / median / p95 over >= 200 further steps), `kernels` (per-kernel roofline from event
+pairs on the launch stream, a profiled eager pass of its own), `frame` (MEASURED tracking+mapping ms/frame of a 31-frame
+sequence with the reference's host sampling run ahead by producer threads, and with device sampling), `roofline`,
+`cpu_baseline`, and the full result goes to bench_detail.json.  `--dump-outputs DIR`: after the timed steps the loop returns
+to its seeded starting state and the timed path's captured graph is replayed once on the first index sets; what it computed
+goes to DIR/<name>.npy (float32; the same inputs, hence the same outputs up to rounding, in every run with the same
+arguments -- see dump_replay).
 
 Prints ONE JSON line (rank 0).
 """
@@ -259,6 +266,13 @@ def parse():
     p.add_argument("--no-variants", action="store_true", help="skip the f32 / dense / unchanged-caller steps")
     p.add_argument("--torch-pose", action="store_true",
                    help="build rays with the reference's eager torch ops (mipsfusion.py:320-322) instead of the fused op")
+    p.add_argument("--full", action="store_true",
+                   help="also measure everything beyond the headline: the profiled eager pass and roofline, step statistics and "
+                        "board state, variants, frame / sequence / inference figures, multi-GPU checks, CPU baseline")
+    p.add_argument("--dump-outputs", metavar="DIR", default=None,
+                   help="after the timed steps, replay the timed path's graph once from the seeded starting state and write "
+                        "what it computed (loss, renders, poses, decoder weights and Adam moments, a seeded sample of the grid "
+                        "and its moments) as DIR/<name>.npy")
     return p.parse_args()
 
 
@@ -357,19 +371,65 @@ class MappingLoop:
         for dst, src in zip(self.static, self.stk):
             torch.index_select(src, 0, idx, out=dst)
 
+    def save_start(self):
+        """Keep the seeded state the loop starts from (model tensors, keyframe poses; the optimisers start empty)."""
+        self._start = [(t, t.detach().clone()) for t in
+                       list(self.model.state_dict(keep_vars=True).values()) + [self.cur_rot, self.cur_trans]]
+
+    @torch.no_grad()
+    def restore_start(self):
+        """Back to the state of save_start(), IN PLACE (a captured graph keeps reading the same tensors): parameters and
+        poses copied back, gradients zeroed, both optimisers as freshly constructed."""
+        for t, s in self._start:
+            t.copy_(s)
+            if t.grad is not None:
+                t.grad.zero_()
+        self.map_opt.reset()
+        self.pose_opt.reset()
+        if self.torch_pose:
+            self.poses_all = torch.cat([self.pose_fixed, qt_to_transform_matrix(self.cur_rot, self.cur_trans)], 0)
+
+    def _state_tensors(self):
+        """every tensor the steps read and write: model tensors, keyframe poses, their gradients, both optimisers' moments
+        and device step counters"""
+        out = []
+        for t in list(self.model.state_dict(keep_vars=True).values()) + [self.cur_rot, self.cur_trans]:
+            out += [t] + ([t.grad] if t.grad is not None else [])
+        for opt in (self.map_opt, self.pose_opt):
+            out += [x for st in opt.state.values() if st for x in (st["exp_avg"], st["exp_avg_sq"])]
+            out += [x for pair in opt._dev.values() for x in pair]
+        return out
+
+    def save_state(self):
+        """A copy of where the loop stands (load_state puts it back in place)."""
+        return {"tensors": [(t, t.detach().clone()) for t in self._state_tensors()], "i": self.i,
+                "steps": [(st, st["step"]) for opt in (self.map_opt, self.pose_opt) for st in opt.state.values() if st]}
+
+    @torch.no_grad()
+    def load_state(self, snap):
+        for t, c in snap["tensors"]:
+            t.copy_(c)
+        for st, n in snap["steps"]:
+            st["step"] = n
+        self.i = snap["i"]
+        if self.torch_pose:
+            self.poses_all = torch.cat([self.pose_fixed, qt_to_transform_matrix(self.cur_rot, self.cur_trans)], 0)
+
     def step_static(self, k):
         rows, owner, noise = (t[k] for t in self.static)
-        return self._iterate(rows, owner, noise, set_to_none=False)
+        # the group's last iteration keeps its results: once captured, they are the graph's static outputs, rewritten by
+        # every replay (dump_replay reads them)
+        return self._iterate(rows, owner, noise, set_to_none=False, keep=k == self.n_inner - 1)
 
     def step(self):
         b = self.i % self.n_sets
-        return self._iterate(self.idx_rows[b], self.idx_owner[b], self.noise[b], set_to_none=True)
+        return self._iterate(self.idx_rows[b], self.idx_owner[b], self.noise[b], set_to_none=True, keep=True)
 
     def batch(self, b):
         """(rays [N,7], owner) of index set b, for the forward-only / CPU legs"""
         return ops.gather_rays(self.table, self.idx_rows[b]), self.idx_owner[b]
 
-    def _iterate(self, rows, owner, noise, set_to_none):
+    def _iterate(self, rows, owner, noise, set_to_none, keep=False):
         cfg = self.cfg
         if self.torch_pose:
             rays_d_cam, target_s, target_d = ops.gather_rays(self.table, rows, split=True)  # fresh rows of the ray table
@@ -382,6 +442,9 @@ class MappingLoop:
                                                 accumulate_in_place=True)
         loss = get_loss_from_ret(ret, cfg["training"])
         backward_from_one(loss, retain_graph=self.torch_pose)     # = loss.backward(), minus autograd's ones_like fill
+        if keep:        # (detached views: what autograd held for the backward is released as before)
+            self.last = {"loss": loss.detach(), "rgb": ret["rgb"].detach(), "depth": ret["depth"].detach(),
+                         "losses": [ret[k].detach() for k in ("rgb_loss", "depth_loss", "sdf_loss", "fs_loss")]}
         self.i += 1
         if self.i % cfg["mapping"]["map_accum_step"] == 0:
             self.map_opt.step(zero_grad=True)           # step + zero_grad (mipsfusion.py:330-335) in one pass
@@ -1025,6 +1088,66 @@ def cpu_baseline(cfg, loop, n_rays, iters, warmup=3):
                       f"{n_rays} of the 4096 rays x 64 samples of the same batch, torch CPU threads = cores"}
 
 
+GRID_SAMPLE = 1 << 20              # hash-grid entries --dump-outputs writes (a fixed, seeded sample of the 9 M)
+
+
+def dump_replay(loop, graphed, last, n_inner):
+    """--dump-outputs: the timed path once more, from inputs that are the same in every run.  After the timed steps the
+    loop goes back IN PLACE to the seeded state it was built with, before
+    the setup iterations -- model, keyframe poses, empty optimisers -- and the captured graph the timed region replayed is
+    replayed once on the first index sets: pose_accum_step iterations (one pose optimiser step among them).  Without graphs
+    the same iterations run eagerly, as the timed region did.  The seeded state is the latest one two runs share: the setup,
+    warm-up and timed steps add with atomics in an order that differs from run to run, and training amplifies those last-bit
+    differences (two runs of 200 timed steps end with losses 4e-3 apart).
+    last: the graph's static outputs of its last iteration (loss, rendered rays, loss terms).  -> float32 host arrays: the
+    loss and its terms, rendered colour and depth of that iteration; the poses, decoder weights (parameters() order,
+    flattened) and both Adam moments of the decoder after it; the same three for a fixed, seeded sample of GRID_SAMPLE
+    hash-grid entries."""
+    i = loop.i
+    loop.restore_start()
+    loop.i = 0
+    if graphed is not None:
+        loop.refill_static()
+        graphed.replay()
+    else:
+        for _ in range(n_inner):
+            loop.step()
+        last = loop.last
+    loop.i = i
+    m, opt = loop.model, loop.map_opt
+    dec, grid = list(m.decoder.parameters()), m.embed_fn.params
+    idx = np.sort(np.random.default_rng(0).choice(grid.numel(), GRID_SAMPLE, replace=False))
+    idx = torch.from_numpy(idx).to(grid.device)
+    arrays = {"loss": last["loss"].reshape(1), "loss_terms": torch.stack([t.reshape(()) for t in last["losses"]]),
+              "rgb": last["rgb"], "depth": last["depth"], "pose_rot": loop.cur_rot, "pose_trans": loop.cur_trans,
+              "decoder_params": torch.cat([p.reshape(-1) for p in dec]),
+              "decoder_adam_m": torch.cat([opt.state[p]["exp_avg"].reshape(-1) for p in dec]),
+              "decoder_adam_v": torch.cat([opt.state[p]["exp_avg_sq"].reshape(-1) for p in dec]),
+              "grid_params_sample": grid.reshape(-1)[idx],
+              "grid_adam_m_sample": opt.state[grid]["exp_avg"].reshape(-1)[idx],
+              "grid_adam_v_sample": opt.state[grid]["exp_avg_sq"].reshape(-1)[idx]}
+    return {k: v.detach().float().cpu().numpy() for k, v in arrays.items()}
+
+
+def dump_outputs(d, loop, graphed, last, n_inner):
+    """--dump-outputs, right after the timed region: dump_replay -> DIR/<name>.npy, the loop's state saved before and put
+    back after, so that whatever runs next (--full) continues from the timed steps' state.  (It runs here, not at the end
+    of the run: the --full measurements re-pack the decoder and re-size the operators' workspaces, buffers outside the
+    graph's own pool that its captured kernels still point at -- a replay after them would read freed memory.)"""
+    snap = loop.save_state()
+    arrays = dump_replay(loop, graphed, last, n_inner)
+    loop.load_state(snap)
+    del snap
+    write_outputs(d, arrays)
+
+
+def write_outputs(d, arrays):
+    os.makedirs(d, exist_ok=True)
+    for k, v in arrays.items():
+        np.save(os.path.join(d, k + ".npy"), v)
+    log(f"outputs of one timed-path group from the seeded state written to {d}: {', '.join(sorted(arrays))}")
+
+
 def pmc_traffic(key="traffic_bytes_per_launch"):
     """HBM bytes per launch from the committed rocprofv3 PMC passes (profiles/pmc_latest.json, written by
     tools/pmc_to_json.py from `tools/pmc.sh`; FETCH_SIZE/WRITE_SIZE are in KiB).  `traffic` applies the guide's gfx950
@@ -1125,11 +1248,12 @@ def _pick(d, keys):
     return {k: d[k] for k in keys if isinstance(d, dict) and k in d and d[k] is not None}
 
 
-def compact_line(out):
+def compact_line(out, detail=True):
     """The ONE line the driver parses, built from the full result `out`: the contract fields, `roofline` (dominant kernel,
     algorithmic AND issued fractions), `cpu_baseline`, the frame metric, the unchanged caller's step and one row of
     (avg_ms, frac) per kernel.  Everything else -- variants, per-kernel detail, sequences, inference -- goes to
-    bench_detail.json beside this script and to stderr.  Always shorter than LINE_LIMIT (tests/test_host_cpu.py)."""
+    bench_detail.json beside this script and to stderr (detail=False: a plain run, which writes no detail file).  Always
+    shorter than LINE_LIMIT (tests/test_host_cpu.py)."""
     line = _pick(out, ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling",
                        "vs_baseline", "dtype", "data"))
     line["vs_baseline"] = out.get("vs_baseline")                  # null is the contract's value when nothing is published
@@ -1190,7 +1314,8 @@ def compact_line(out):
         if mg.get("ranks"):
             line["multi_gpu"]["ranks"] = _pick(mg["ranks"], ("world_size", "backend", "distinct_devices"))
     line["scaling_curve"] = str(out.get("scaling_curve", ""))[:160]
-    line["detail"] = "bench_detail.json (full result: variants, per-kernel rows, sequences, inference); also on stderr"
+    if detail:
+        line["detail"] = "bench_detail.json (full result: variants, per-kernel rows, sequences, inference); also on stderr"
     text = json.dumps(line, separators=(",", ":"))
     # never over the limit: drop the optional blocks, least important first
     for k in ("gradient_sparsity", "step_ms_stats", "variants_ms_per_step", "kernels_avg_ms_frac", "multi_gpu", "forward_only", "frame"):
@@ -1202,12 +1327,16 @@ def compact_line(out):
     return text
 
 
-def emit(out):
+def emit(out, full=True):
     """full result -> bench_detail.json + stderr; the compact line -> stdout (last line).  Rank 0 only: the other ranks' results
-    go to stderr (the launcher forwards ONE line, and the detail file must be that rank's)."""
+    go to stderr (the launcher forwards ONE line, and the detail file must be that rank's).  full=False (a plain run): the
+    line alone."""
     if int(os.environ.get("RANK", "0")) != 0:
         sys.stderr.write(f"[bench detail rank {os.environ.get('RANK')}] " + json.dumps(out) + "\n")
         sys.stderr.flush()
+        return
+    if not full:
+        print(compact_line(out, detail=False), flush=True)
         return
     detail = json.dumps(out)
     for d in (ROOT, os.path.join(ROOT, "gpurun_out")):
@@ -1253,6 +1382,58 @@ def launch_ranks(n):
         raise SystemExit("the ranks printed no JSON line")
     print(last_json, flush=True)
     raise SystemExit(0)
+
+
+def full_extras(args, out, cfg, model, loop, dev, stream, use_graph, world, ms_step, prof, eager_elapsed, step_stats,
+                board, variants, multi, ranks_info):
+    """--full: everything beyond the headline, added to the result `out` (rank 0, after the timed steps and the variants)."""
+    M = N_RAYS * N_SAMPLES
+    live_share = ops.last_live_tile_share()
+    pair_share = ops.last_live_record_share()
+    kernels, roofline = kernel_table(prof, M, model.decoder_precision, live_share, pair_share)
+
+    fwd_rate, fwd_ms = forward_only_rate(model, loop, dev)
+    log(f"forward-only {fwd_ms:.3f} ms")
+    out.update({
+        "step_ms_stats": step_stats,
+        "board": board,
+        "value_at_median_step": None if not step_stats else round(M * world / (step_stats["median"] * 1e-3), 1),
+        "eager_ms_per_step": round(eager_elapsed / args.steps * 1e3, 4),
+        "forward_only": {"value": round(fwd_rate, 1), "unit": "rays*samples/s", "ms": round(fwd_ms, 4)},
+        "decoder_gemm_forward": decoder_gemm_rates(model, dev, M),
+        "variants": variants,
+        "roofline": roofline, "kernels": kernels,
+        "gradient_sparsity": {"live_32_sample_tiles": None if live_share is None else round(live_share, 4),
+                              "live_sample_level_pairs": None if pair_share is None else round(pair_share, 4),
+                              "note": "samples behind the truncation band carry no loss term and no rendering weight: "
+                                      "exactly zero gradient; the backward chain, the weight-gradient kernel, dx and the grid "
+                                      "scatter skip them (tiles / records); `kernels[*].achieved` counts the units a launch "
+                                      "processed (live units at the full cost, dead units at the cost of finding them dead), "
+                                      "`frac_full_batch` prices every unit as live"},
+    })
+    if not args.no_frame_estimate:
+        out["frame"] = frame_estimate(cfg, model, loop, dev, ms_step, stream if use_graph else None)
+        log("iteration-level frame numbers done")
+        if args.seq_frames > 1 and use_graph:
+            seq = measured_sequence(args.seq_frames, dev, stream)
+            out["frame"]["measured_sequence"] = seq
+            # the opt-in fast arithmetics next to it: f16x3 training, plain-f16 RandomOptimizer rounds (round 3's headline mode)
+            fast = measured_sequence(args.seq_frames, dev, stream, samplers=("reference",), decoder_precision="f16x3", ro_precision="f16")
+            out["frame"]["measured_sequence_fast_mode"] = fast["reference"]
+            out["frame"]["ms_per_frame_reference_sampling"] = seq["reference"]["ms_per_frame_mean"]
+            out["frame"]["ms_per_frame_device_sampling"] = seq["device"]["ms_per_frame_mean"]
+            out["frame"]["tracking_plus_mapping_ms_per_frame"] = seq["reference"]["ms_per_frame_mean"]
+            log("measured sequences done")
+            if args.config3_frames > 1:
+                out["frame"]["config3_multi_submap"] = measured_config3(args.config3_frames, dev, stream)
+                log(f"config 3 done: {out['frame']['config3_multi_submap']['ms_per_frame_mean']} ms/frame")
+        out["inference"] = inference_rates(cfg, model, dev)
+        log("inference consumers done")
+    if multi is not None:
+        multi["ranks"] = ranks_info
+        out["multi_gpu"] = multi
+    if world == 1 and args.cpu_rays > 0:
+        out["cpu_baseline"] = cpu_baseline(cfg, loop, args.cpu_rays, args.cpu_iters, args.cpu_warmup)
 
 
 def main():
@@ -1303,12 +1484,14 @@ def main():
     use_graph = not args.no_graph and not args.torch_pose and args.steps % cfg["mapping"]["pose_accum_step"] == 0
     # one fresh batch for every step of every pass (setup, warm-ups, eager pass, graph pass, stats pass); beyond 1024
     # sets the sequence wraps around (a 4 ms host draw per set would otherwise dominate the run time of long benches)
-    n_sets = min(1024, args.setup_iters + 3 * args.warmup + 2 * args.steps + args.stats_steps + 16)
+    n_sets = min(1024, args.setup_iters + 3 * args.warmup + 2 * args.steps + (args.stats_steps if args.full else 0) + 16)
     t_draw = time.perf_counter()
     idx_rows, idx_owner = draw_index_sets(cfg, frames, db, R, n_sets)
     log(f"{n_sets} index sets drawn on the host with the reference samplers in {time.perf_counter() - t_draw:.1f}s")
     loop = MappingLoop(cfg, model, poses, table, idx_rows, idx_owner, dev, torch_pose=args.torch_pose,
                        capturable=use_graph)
+    if args.dump_outputs:
+        loop.save_start()
     log("setup iterations")
     for _ in range(args.setup_iters):
         loop.step()
@@ -1329,33 +1512,40 @@ def main():
             dist.barrier()
         torch.cuda.synchronize()
 
-    # ---- eager pass: K steps with per-kernel event pairs on the launch stream (kernel durations for the roofline)
-    ops.PROFILE = {}
-    barrier()
-    t0 = time.perf_counter()
-    for k in range(args.steps):
-        loop.step()
-        if (k + 1) % ba_round == 0:
-            exchange_poses()
-    barrier()
-    eager_elapsed = time.perf_counter() - t0
-    prof = ops.profile_summary()
-    ops.PROFILE = None
-    log(f"eager timed region: {args.steps} steps in {eager_elapsed * 1e3:.1f} ms")
+    # ---- eager pass: K steps with per-kernel event pairs on the launch stream (kernel durations for the roofline; --full),
+    #      the headline itself when the steps are not graphed (a plain run then times them without the event pairs)
+    prof, eager_elapsed = None, None
+    graphed, static_last, n_inner = None, None, cfg["mapping"]["pose_accum_step"]
+    if args.full or not use_graph:
+        ops.PROFILE = {} if args.full else None
+        barrier()
+        t0 = time.perf_counter()
+        for k in range(args.steps):
+            loop.step()
+            if (k + 1) % ba_round == 0:
+                exchange_poses()
+        barrier()
+        eager_elapsed = time.perf_counter() - t0
+        if args.full:
+            prof = ops.profile_summary()
+        ops.PROFILE = None
+        log(f"eager timed region: {args.steps} steps in {eager_elapsed * 1e3:.1f} ms")
+        if args.dump_outputs and not use_graph and rank == 0:
+            dump_outputs(args.dump_outputs, loop, None, None, n_inner)
     elapsed, step_stats, board = eager_elapsed, None, None
 
     # ---- graph pass (the number reported as `value`): the same K steps as hipGraph replays of pose_accum_step
     #      iterations; fresh ray batches are copied into the static input buffers before every replay
     if use_graph:
-        n_inner = cfg["mapping"]["pose_accum_step"]
         loop.make_static(n_inner)
         loop.refill_static()
         graphed = GraphedSteps(loop.step_static, n_inner, stream=stream)
+        static_last = loop.last                      # the captured last iteration's outputs (--dump-outputs)
         for _ in range(max(1, args.warmup // n_inner)):
             loop.refill_static()
             graphed.replay()
         barrier()
-        board_sampler = BoardSampler(dev.index or 0).__enter__()
+        board_sampler = BoardSampler(dev.index or 0).__enter__() if args.full else None
         t0 = time.perf_counter()
         for r in range(args.steps // n_inner):
             loop.refill_static()
@@ -1365,6 +1555,9 @@ def main():
         barrier()
         elapsed = time.perf_counter() - t0
         log(f"graph timed region: {args.steps} steps in {elapsed * 1e3:.1f} ms")
+        if args.dump_outputs and rank == 0:
+            dump_outputs(args.dump_outputs, loop, graphed, static_last, n_inner)
+    if use_graph and args.full:
         # ---- spread: further steps, every replay (= n_inner steps incl. its input refill) bracketed by an event pair
         n_rep = max(1, args.stats_steps // n_inner)
         ev = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in range(n_rep)]
@@ -1383,7 +1576,7 @@ def main():
     # ---- the same step under the two switches the headline depends on, and the unchanged caller (N = 1 only)
     variants = None
     headline_precision = model.decoder_precision
-    if use_graph and world == 1 and not args.no_variants:
+    if args.full and use_graph and world == 1 and not args.no_variants:
         variants = {}
         M_ = N_RAYS * N_SAMPLES
 
@@ -1424,7 +1617,7 @@ def main():
         dist.all_gather(allr, mine)
         per_rank_ms = [round(float(t), 4) for t in allr]
     elapsed = mdist.max_over_ranks(elapsed, dev)
-    multi = multi_gpu_checks(cfg, model, dev, rank, world) if world > 1 else None
+    multi = multi_gpu_checks(cfg, model, dev, rank, world) if world > 1 and args.full else None
     if multi is not None:
         multi["ms_per_step_of_each_rank"] = per_rank_ms
 
@@ -1437,23 +1630,14 @@ def main():
     ms_step = elapsed / args.steps * 1e3
     value = M * args.steps * world / elapsed
 
-    live_share = ops.last_live_tile_share()
-    pair_share = ops.last_live_record_share()
-    kernels, roofline = kernel_table(prof, M, headline_precision, live_share, pair_share)
-
-    fwd_rate, fwd_ms = forward_only_rate(model, loop, dev)
-    log(f"forward-only {fwd_ms:.3f} ms")
     out = {
         "metric": "rays*samples/s per GPU, full optimisation iteration (fwd + bwd + pose+map Adam), 4096 rays x 64 samples, 640x480 RGB-D",
         "value": round(value, 1), "unit": "rays*samples/s", "n_gpus": world, "steps": args.steps,
         "warmup": args.warmup, "ms_per_step": round(ms_step, 4),
         "launch": "hipGraph replay of pose_accum_step iterations" if use_graph else "eager",
-        "step_ms_stats": step_stats,
-        "board": board,
-        "value_at_median_step": None if not step_stats else round(M * world / (step_stats["median"] * 1e-3), 1),
         "batches": "a fresh ray batch every step: rows gathered in-step from the HBM ray table (4 keyframes x 30 000 rays "
                    "+ current frame) by host-drawn index sets (reference samplers), indices and jitter resident in HBM",
-        "eager_ms_per_step": round(eager_elapsed / args.steps * 1e3, 4), "higher_is_better": True, "scaling": "weak",
+        "higher_is_better": True, "scaling": "weak",
         "vs_baseline": None,
         "dtype": DTYPE_OF[headline_precision],
         "data": "synthetic",
@@ -1463,44 +1647,13 @@ def main():
                    "parallelism": f"submap-per-gpu x{world}" if world > 1 else "single gpu",
                    "ray_build": "torch eager ops" if args.torch_pose else "row gather + pose rays + sample placement in one kernel",
                    "host_cpus": f"{len(HOST_CPUS)} least-busy CPUs of one NUMA node ({HOST_CPUS[0]}..{HOST_CPUS[-1]})" if HOST_CPUS else "unconfined"},
-        "forward_only": {"value": round(fwd_rate, 1), "unit": "rays*samples/s", "ms": round(fwd_ms, 4)},
-        "decoder_gemm_forward": decoder_gemm_rates(model, dev, M),
-        "variants": variants,
-        "roofline": roofline, "kernels": kernels,
-        "gradient_sparsity": {"live_32_sample_tiles": None if live_share is None else round(live_share, 4),
-                              "live_sample_level_pairs": None if pair_share is None else round(pair_share, 4),
-                              "note": "samples behind the truncation band carry no loss term and no rendering weight: "
-                                      "exactly zero gradient; the backward chain, the weight-gradient kernel, dx and the grid "
-                                      "scatter skip them (tiles / records); `kernels[*].achieved` counts the units a launch "
-                                      "processed (live units at the full cost, dead units at the cost of finding them dead), "
-                                      "`frac_full_batch` prices every unit as live"},
     }
-    if not args.no_frame_estimate:
-        out["frame"] = frame_estimate(cfg, model, loop, dev, ms_step, stream if use_graph else None)
-        log("iteration-level frame numbers done")
-        if args.seq_frames > 1 and use_graph:
-            seq = measured_sequence(args.seq_frames, dev, stream)
-            out["frame"]["measured_sequence"] = seq
-            # the opt-in fast arithmetics next to it: f16x3 training, plain-f16 RandomOptimizer rounds (round 3's headline mode)
-            fast = measured_sequence(args.seq_frames, dev, stream, samplers=("reference",), decoder_precision="f16x3", ro_precision="f16")
-            out["frame"]["measured_sequence_fast_mode"] = fast["reference"]
-            out["frame"]["ms_per_frame_reference_sampling"] = seq["reference"]["ms_per_frame_mean"]
-            out["frame"]["ms_per_frame_device_sampling"] = seq["device"]["ms_per_frame_mean"]
-            out["frame"]["tracking_plus_mapping_ms_per_frame"] = seq["reference"]["ms_per_frame_mean"]
-            log("measured sequences done")
-            if args.config3_frames > 1:
-                out["frame"]["config3_multi_submap"] = measured_config3(args.config3_frames, dev, stream)
-                log(f"config 3 done: {out['frame']['config3_multi_submap']['ms_per_frame_mean']} ms/frame")
-        out["inference"] = inference_rates(cfg, model, dev)
-        log("inference consumers done")
-    if multi is not None:
-        multi["ranks"] = ranks_info
-        out["multi_gpu"] = multi
     out["scaling_curve"] = ("unmeasured: no multi-GPU node has been available to this build; N > 1 has run only as two gloo "
                             "ranks sharing one GPU (tests/test_gpu_configs.py)") if world == 1 else "this line is one point of it"
-    if world == 1 and args.cpu_rays > 0:
-        out["cpu_baseline"] = cpu_baseline(cfg, loop, args.cpu_rays, args.cpu_iters, args.cpu_warmup)
-    emit(out)
+    if args.full:
+        full_extras(args, out, cfg, model, loop, dev, stream, use_graph, world, ms_step, prof, eager_elapsed,
+                    step_stats, board, variants, multi, ranks_info)
+    emit(out, full=args.full)
     if dist is not None:
         dist.barrier()
         dist.destroy_process_group()

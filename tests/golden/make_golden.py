@@ -14,6 +14,7 @@ Files written
                      + gradients, BASELINE config 1 (256 rays x 16 samples, hash 2^10)
   scene_s75.npz      same with the reference's default S = 50 + 25 (> one wavefront), 64 rays
   scene_nd0.npz      same with training.n_samples_d = 0 (scene_rep.py:166-167: the depth-guided samples alone), 64 rays
+  fresh_seed.npz     model/scene_rep.py forward (train) of a model the reference's constructor initialised, seed 123
   adam.npz           torch.optim.Adam with the two param groups of mipsfusion.py:580-584
   quaternion.npz     geometry_helper.py:11-17 qt_to_transform_matrix (+ grads) [pytorch3d unpinned]
   ba_trace.npz       loss-per-iteration trace of a 6-iteration local-BA-style loop (mipsfusion.py:293-342)
@@ -47,6 +48,9 @@ def seed_all(s=0):
     torch.manual_seed(s)
 
 
+FILE_LIMIT = 1 << 20          # no committed file reaches 1 MiB
+
+
 def save(name, **arrays):
     out = {}
     for k, v in arrays.items():
@@ -56,6 +60,25 @@ def save(name, **arrays):
     path = os.path.join(HERE, name)
     np.savez_compressed(path, **out)
     print(f"{name}: {os.path.getsize(path) / 1024:.0f} KiB, {len(out)} arrays")
+    n = 1
+    while os.path.exists(path) and os.path.getsize(path) >= FILE_LIMIT:
+        # too large: <stem>.part1.npz, .part2.npz, ... (consecutive arrays of about equal size), which
+        # tests/conftest.py::load_golden reads back as one fixture
+        os.remove(path)
+        n += 1
+        keys, total = list(out), sum(v.nbytes for v in out.values())
+        groups, acc = [[] for _ in range(n)], 0
+        for k in keys:
+            groups[min(n - 1, int(acc * n / max(total, 1)))].append(k)
+            acc += out[k].nbytes
+        parts = [os.path.join(HERE, f"{name[:-4]}.part{i + 1}.npz") for i in range(n)]
+        for p, grp in zip(parts, groups):
+            np.savez_compressed(p, **{k: out[k] for k in grp})
+        if all(os.path.getsize(p) < FILE_LIMIT for p in parts):
+            print(f"  in {n} parts: " + ", ".join(f"{os.path.getsize(p) / 1024:.0f} KiB" for p in parts))
+            break
+        for p in parts:
+            os.remove(p)
 
 
 class FixedRand:
@@ -198,6 +221,34 @@ def scene_case(cfg, n_rays, name, seed):
             if v.numel():
                 arrays[f"{tag}.g.{k}"] = v.grad
     save(name, **arrays)
+
+
+def gen_fresh_seed():
+    """The training forward of the reference's JointEncoding at a seed no other fixture uses (model initialised by the
+    reference's constructor at torch seed 123, grid values N(0, 0.2^2), 64 random rays with three of zero depth): state dict,
+    inputs and the returned rgb / depth / losses."""
+    cfg = synth.config_plumbing()
+    torch.manual_seed(123)
+    bb = torch.from_numpy(np.array(cfg["mapping"]["bound"]))
+    nf = torch.from_numpy(np.array(cfg["mapping"]["localMLP_max_len"]))
+    model = ref.scene_rep.JointEncoding(cfg, bb, nf)
+    with torch.no_grad():
+        model.embed_fn.params.copy_(torch.randn_like(model.embed_fn.params) * 0.2)
+    N, S = 64, 16
+    ro = torch.rand(N, 3) * 0.2
+    rd = torch.nn.functional.normalize(torch.randn(N, 3), dim=-1)
+    rgb, d = torch.rand(N, 3), torch.rand(N, 1) * 1.5
+    d[:3] = 0
+    noise = torch.rand(N, S)
+    arrays = dict(rays_o=ro, rays_d=rd, target_rgb=rgb, target_d=d, noise=noise, bound=bb, half_len=nf)
+    for k, v in model.state_dict().items():
+        arrays["w." + k] = v
+    model.train()
+    with FixedRand(noise):
+        r = model.forward(ro, rd, rgb, d)
+    for k in ("rgb", "depth", "rgb_loss", "depth_loss", "sdf_loss", "fs_loss"):
+        arrays["train." + k] = r[k]
+    save("fresh_seed.npz", **arrays)
 
 
 def gen_scene_nd0():
@@ -502,6 +553,7 @@ if __name__ == "__main__":
     c75["training"].update(n_samples_d=50, n_range_d=25, n_samples=75)
     scene_case(c75, 64, "scene_s75.npz", seed=9)
     gen_scene_nd0()
+    gen_fresh_seed()
     gen_adam()
     gen_quaternion()
     gen_ba_trace()

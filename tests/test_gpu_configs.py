@@ -670,7 +670,7 @@ def test_two_process_run_exercises_every_sharding(dev):
     env = dict(os.environ, MIPSF_BENCH_BACKEND="gloo", HSA_ENABLE_IPC_MODE_LEGACY="0")
     for k in ("WORLD_SIZE", "RANK", "LOCAL_RANK"):
         env.pop(k, None)
-    cmd = [sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "10",
+    cmd = [sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "10", "--full",
            "--warmup", "5", "--setup-iters", "10", "--cpu-rays", "0", "--no-frame-estimate"]
     res = subprocess.run(cmd, cwd=root, env=env, capture_output=True, text=True, timeout=900)
     assert res.returncode == 0, res.stderr[-3000:]
@@ -692,3 +692,52 @@ def test_two_process_run_exercises_every_sharding(dev):
     assert rdp["params_equal_over_ranks"] is True and rdp["rays_per_rank"] == 2048
     assert rdp["loss_first_last"][1] < rdp["loss_first_last"][0]
     assert mg["pose_all_gather_ms"] > 0 and mg["pose_grad_all_reduce_ms"] > 0 and len(mg["ms_per_step_of_each_rank"]) == 2
+
+
+def test_plain_bench_run_times_its_steps_and_dumps_a_reproducible_step(dev, tmp_path):
+    """`python bench.py --gpus 1 --steps K --warmup W --dump-outputs DIR`: the plain run prints the contract fields for the K
+    graph-replayed steps, then replays the timed graph once from the seeded starting state and writes what it computed as
+    float32 arrays (64 MB at most).  Two runs with the same arguments write the same arrays up to rounding; the loss is the
+    configuration's weighting of its terms."""
+    import json
+    import os
+    import subprocess
+    import sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    dumps = []
+    for run in ("a", "b"):
+        out_dir = str(tmp_path / run)
+        cmd = [sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--steps", "10", "--warmup", "5",
+               "--setup-iters", "5", "--dump-outputs", out_dir]
+        res = subprocess.run(cmd, cwd=root, capture_output=True, text=True, timeout=600)
+        assert res.returncode == 0, res.stderr[-3000:]
+        line = json.loads([ln for ln in res.stdout.splitlines() if ln.startswith("{")][-1])
+        for k in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step"):
+            assert line.get(k) is not None, k
+        assert line["steps"] == 10 and line["warmup"] == 5 and line["launch"].startswith("hipGraph")
+        assert abs(line["value"] * line["ms_per_step"] * 1e-3 - 4096 * 64) < 1e-3 * 4096 * 64
+        dumps.append({n[:-4]: np.load(os.path.join(out_dir, n)) for n in os.listdir(out_dir)})
+    a, b = dumps
+    assert set(a) == {"loss", "loss_terms", "rgb", "depth", "pose_rot", "pose_trans", "decoder_params", "decoder_adam_m",
+                      "decoder_adam_v", "grid_params_sample", "grid_adam_m_sample", "grid_adam_v_sample"}
+    assert all(v.dtype == np.float32 and np.isfinite(v).all() for v in a.values())
+    assert sum(v.nbytes for v in a.values()) <= 64 * 2 ** 20
+    assert a["rgb"].shape == (4096, 3) and a["depth"].shape == (4096,) and a["grid_params_sample"].shape == (1 << 20,)
+    assert a["decoder_params"].shape == a["decoder_adam_v"].shape == (36577,) and a["pose_rot"].shape == (4, 4)
+    # run to run, as max |a - b| / max |b| (measured at 1e-6 and below; the loss, its terms and the poses bit for bit): the
+    # forward outputs and the moments carry only reordered sums.  The parameters after Adam's update (divided by
+    # sqrt(v) + eps) carry a near-zero gradient's last-bit difference further in single entries: up to 1.7e-3 of the grid's
+    # maximum and 6e-5 of the decoder's, 5e-6 and 1e-6 in the L2 norm -- gated on both.
+    tol = dict(loss=1e-6, loss_terms=1e-6, pose_rot=1e-6, pose_trans=1e-6, rgb=1e-5, depth=1e-5, decoder_adam_m=1e-5,
+               decoder_adam_v=1e-5, grid_adam_m_sample=1e-5, grid_adam_v_sample=1e-5, decoder_params=5e-4,
+               grid_params_sample=1e-2)
+    for k in a:
+        assert np.abs(a[k]).max() > 0, k
+        d = a[k].astype(np.float64) - b[k]
+        err = float(np.abs(d).max() / np.abs(b[k]).max())
+        assert err <= tol[k], f"{k}: two runs differ by {err:.2e} of the maximum (gate {tol[k]:.0e})"
+        l2 = float(np.linalg.norm(d) / np.linalg.norm(b[k].astype(np.float64)))
+        assert l2 <= 1e-4, f"{k}: two runs differ by {l2:.2e} in the L2 norm"
+    tr = synth.config_headline()["training"]
+    w = np.array([tr["rgb_weight"], tr["depth_weight"], tr["sdf_weight"], tr["fs_weight"]], dtype=np.float64)
+    np.testing.assert_allclose(a["loss"][0], float(w @ a["loss_terms"].astype(np.float64)), rtol=1e-5)

@@ -1,13 +1,12 @@
 """CPU: pin the oracle (oracle/path_cpu.py, oracle/p3d_cpu.py) against the golden vectors the
-REFERENCE produced (tests/golden/make_golden.py), and -- when /root/reference is present, i.e. in the
-build container -- against the reference imported live."""
+REFERENCE produced (tests/golden/make_golden.py)."""
 import math
 
 import numpy as np
 import pytest
 import torch
 
-from oracle import p3d_cpu, path_cpu, ref_import, tcnn_cpu
+from oracle import p3d_cpu, path_cpu, tcnn_cpu
 from mipsfusion_amd import synth
 
 from .conftest import load_golden
@@ -216,35 +215,15 @@ def test_frequency_oracle_values():
     assert y.shape == (1, 12)
 
 
-@pytest.mark.skipif(not ref_import.available(), reason="reference tree only exists in the build container")
-def test_oracle_equals_live_reference_on_fresh_seed():
-    """Beyond the committed vectors: a fresh seed, live against the reference's Python."""
-    ref = ref_import.load()
+def test_oracle_equals_reference_on_fresh_seed():
+    """Beyond the scene fixtures: a model the reference's own constructor initialised at another seed, 64 random rays (three
+    of zero depth) -- the reference's training forward recorded in tests/golden/fresh_seed.npz."""
+    g = load_golden("fresh_seed.npz")
     cfg = synth.config_plumbing()
-    torch.manual_seed(123)
-    bb = torch.from_numpy(np.array(cfg["mapping"]["bound"]))
-    nf = torch.from_numpy(np.array(cfg["mapping"]["localMLP_max_len"]))
-    model = ref.scene_rep.JointEncoding(cfg, bb, nf)
-    with torch.no_grad():
-        model.embed_fn.params.copy_(torch.randn_like(model.embed_fn.params) * 0.2)
-    mine = path_cpu.CpuScene(cfg, bb, nf)
-    mine.load_state_dict(model.state_dict())
-    N, S = 64, 16
-    ro = torch.rand(N, 3) * 0.2
-    rd = torch.nn.functional.normalize(torch.randn(N, 3), dim=-1)
-    rgb, d = torch.rand(N, 3), torch.rand(N, 1) * 1.5
-    d[:3] = 0
-    noise = torch.rand(N, S)
-    orig = torch.rand
-    torch.rand = lambda *a, **k: noise.clone()
-    try:
-        model.train()
-        r = model.forward(ro, rd, rgb, d)
-    finally:
-        torch.rand = orig
-    o = mine.train_forward(ro, rd, rgb, d, noise, 0.01)
+    mine = scene_from(g, cfg)
+    o = mine.train_forward(T(g["rays_o"]), T(g["rays_d"]), T(g["target_rgb"]), T(g["target_d"]), T(g["noise"]), 0.01)
     for k in ("rgb", "depth", "rgb_loss", "depth_loss", "sdf_loss", "fs_loss"):
-        close(o[k].detach(), r[k].detach(), rtol=2e-5, atol=1e-7)
+        close(o[k].detach(), g["train." + k], rtol=2e-5, atol=1e-7)
 
 
 def test_plain_c_restatement_agrees_bit_for_bit():

@@ -2,6 +2,7 @@
 # GPU box: tools/micro/run_variants.sh <kernel-grep> <name>...   ("base" = the in-tree library)
 # runs the headline bench once per experiment library and prints ms/step + the matching per-kernel times
 PAT=$1; shift
+BENCH_ARGS="--full ${BENCH_ARGS}"     # the per-kernel table comes from the benchmark's profiled eager pass
 cd $GRAFT_REPO_ROOT
 mkdir -p gpurun_out/var
 for v in "$@"; do

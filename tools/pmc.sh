@@ -4,6 +4,7 @@
 TAG=$1
 shift
 if [ $# -gt 0 ]; then PROG="$GRAFT_REPO_ROOT/$1"; shift; ARGS="$@"; else PROG="$GRAFT_REPO_ROOT/bench.py"; ARGS="--steps 5 --warmup 5 --stats-steps 10 --setup-iters 4 --cpu-rays 0 --no-frame-estimate --no-variants"; fi
+case "$PROG" in */bench.py) ARGS="--full $ARGS";; esac       # every pass of the benchmark, not only its timed steps
 OUT=$GRAFT_REPO_ROOT/gpurun_out/pmc_$TAG
 mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp

@@ -2,6 +2,7 @@
 # usage: tools/profile.sh <tag> [bench args...]   (run on the GPU box through gpurun)
 # rocprofv3 kernel trace + stats of bench.py; only the small summaries are copied into gpurun_out/.
 TAG=$1; shift
+set -- --full "$@"         # every pass of the benchmark (eager, graphed, statistics, variants), not only its timed steps
 OUT=$GRAFT_REPO_ROOT/gpurun_out/prof_$TAG
 mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp
