@@ -76,6 +76,7 @@ typedef struct mipsf_grid_meta {
 #define MIPSF_SIZE_RENDER_PARTIAL 9           /* n = N: `partial` of mipsf_render_fwd = max(8 N, 18 ceil(N / 16))           */
 #define MIPSF_SIZE_PLACE_POSE_SCRATCH 10      /* n = N, a = F, b = K: mipsf_place_pose_bwd                                  */
 #define MIPSF_SIZE_POSE_RAYS_SCRATCH 11       /* n = N, a = F, b = K: mipsf_pose_rays_bwd                                   */
+#define MIPSF_SIZE_HASHGRID_DET_SCRATCH 12    /* n = M, a = (dx != NULL), meta: mipsf_hashgrid_bwd with MIPSF_HG_DETERMINISTIC */
 uint64_t mipsf_buffer_size(int which, uint32_t n, uint32_t a, uint32_t b, const mipsf_grid_meta* meta_host);
 
 /* --------------------------------------------------------------- hash grid (a5) */
@@ -109,9 +110,31 @@ int mipsf_hashgrid_dx_from_jac(const float* jac, const float* dout, float* dx, c
  *   flags      MIPSF_HG_DPARAMS_ZERO: the caller vouches that dparams is all zero on entry (the gradient buffer of an optimiser
  *              that clears it, a fresh allocation): table slices are stored instead of read-modify-written.
  *              MIPSF_HG_ROUTED: `scratch` was filled by mipsf_hashgrid_route for this x (the routing third of the call
- *              depends on x only and may run earlier, e.g. on a second stream next to the forward pass) */
+ *              depends on x only and may run earlier, e.g. on a second stream next to the forward pass)
+ *              MIPSF_HG_DETERMINISTIC: the fixed-order scatter below instead of the LDS slices; `scratch` is then
+ *              MIPSF_SIZE_HASHGRID_DET_SCRATCH floats and `counters` is ignored.  Refused with MIPSF_HG_ROUTED.
+ *
+ * DETERMINISTIC CONTRACT (MIPSF_HG_DETERMINISTIC).  For every level l, entry e of the level and feature f:
+ *   contributions  for each sample i in ascending order, then corner c = 0..7 with idx(l, i, c) == e:
+ *                  v = (double)w_c(x_i, l) * (double)g(i, l, f), the exact product of the fp32 weight the forward uses
+ *                  (locate, then corner_weights in dimension order) and the fp32 incoming gradient.  A (sample, level) pair
+ *                  whose two gradients are both exactly zero adds nothing (its products are +-0 and the sum starts at +0:
+ *                  no bit changes); every other pair adds all 8 corners, w == 0 included (0 * inf = NaN, as tcnn_cpu)
+ *   summation      an entry's ordered contributions are cut into pieces of MIPSF_HG_DET_PIECE items from its first one; each
+ *                  piece is summed left to right in fp64 from +0, the piece sums are added left to right in fp64 from +0,
+ *                  and the total S is rounded once: s = (float)S
+ *   write-back     with MIPSF_HG_DPARAMS_ZERO dparams[e] = s, else dparams[e] = dparams[e] + s (an fp32 add); an entry with no
+ *                  contribution is not written
+ *   depends on     (x, dout, dparams on entry, meta, M, layout, flags) only: not on the stream, other work on the device,
+ *                  hipGraph capture, the `counters` block or the CU count (no launch dimension is derived from it)
+ *   limit          8 * n_levels * M <= MIPSF_HG_DET_MAX_ITEMS (M <= 2^24 at 16 levels); a larger batch is refused
+ *   dx             unchanged: the per-level partials summed in level order, as without the flag
+ * Cost: a store pass, a radix sort of 8 L M keys and the per-entry sums. */
 #define MIPSF_HG_DPARAMS_ZERO 1u
 #define MIPSF_HG_ROUTED 2u
+#define MIPSF_HG_DETERMINISTIC 4u
+#define MIPSF_HG_DET_PIECE 512
+#define MIPSF_HG_DET_MAX_ITEMS (1ull << 31)
 typedef struct mipsf_hashgrid_bwd_args {
     uint32_t struct_size;
     uint32_t M;
@@ -275,8 +298,15 @@ int mipsf_decoder_bwd_chain16(const mipsf_decoder_chain16_args* args_host, void*
  *   packed16    nullable (F16X3 / BF16X6): H1 is not read from `saved` but RECOMPUTED from x with the forward's own layer-1
  *               operand images (bit-identical) -- the companion of the lean record
  *   tile_live   nullable: only the tiles the chain listed
- *   flags       MIPSF_WGRAD_LEAN_DACT: `dact` is the lean gradient record (packed16 given) */
+ *   flags       MIPSF_WGRAD_LEAN_DACT: `dact` is the lean gradient record (packed16 given)
+ *               MIPSF_WGRAD_DETERMINISTIC: the weight gradients depend on the inputs and the device's CU count only
+ *               (deterministic training).  Each of the eight lists in `tile_live` (if given) is first put in ascending tile
+ *               order IN PLACE (members and counts unchanged): the chain appends tiles in the order they finish and this
+ *               kernel deals list positions to its workgroups.  The per-workgroup records are then summed in block order by
+ *               one thread per gradient element (the default reduce meets in float atomics).  M <= MIPSF_TILE_ORDER_MAX_M */
 #define MIPSF_WGRAD_LEAN_DACT 1u
+#define MIPSF_WGRAD_DETERMINISTIC 2u
+#define MIPSF_TILE_ORDER_MAX_M (1u << 27)
 typedef struct mipsf_decoder_wgrad16_args {
     uint32_t struct_size;
     uint32_t M;

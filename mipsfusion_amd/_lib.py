@@ -84,7 +84,15 @@ RENDER_BWD_KEEP_IF_UNIT = 1
 # mipsf_buffer_size(which, n, a, b, meta): MIPSF_SIZE_* of include/mipsf.h
 (SIZE_HASHGRID_BWD_SCRATCH, SIZE_HASHGRID_COUNTER_WORDS, SIZE_DECODER_PACKED, SIZE_DECODER_SAVED, SIZE_DECODER_DACT,
  SIZE_DECODER_WGRAD_PARTIAL, SIZE_DECODER_PACKED16, SIZE_DECODER_TILE_WORDS, SIZE_RENDER_PARTIAL, SIZE_PLACE_POSE_SCRATCH,
- SIZE_POSE_RAYS_SCRATCH) = range(1, 12)
+ SIZE_POSE_RAYS_SCRATCH, SIZE_HASHGRID_DET_SCRATCH) = range(1, 13)
+
+# mipsf_hashgrid_bwd flags (MIPSF_HG_*) and the deterministic scatter's constants
+HG_DPARAMS_ZERO, HG_ROUTED, HG_DETERMINISTIC = 1, 2, 4
+HG_DET_PIECE = 512
+HG_DET_MAX_ITEMS = 1 << 31
+TILE_ORDER_MAX_M = 1 << 27
+# mipsf_decoder_wgrad16 flags (MIPSF_WGRAD_*)
+WGRAD_LEAN_DACT, WGRAD_DETERMINISTIC = 1, 2
 
 
 ADAM_MAX_TENSORS = 16

@@ -42,9 +42,11 @@ int mipsf_abi_version(void) { return MIPSF_ABI_VERSION; }
 uint64_t mipsf_buffer_size(int which, uint32_t n, uint32_t a, uint32_t b, const mipsf_grid_meta* meta) {
     switch (which) {
         case MIPSF_SIZE_HASHGRID_BWD_SCRATCH:
-        case MIPSF_SIZE_HASHGRID_COUNTER_WORDS: {
+        case MIPSF_SIZE_HASHGRID_COUNTER_WORDS:
+        case MIPSF_SIZE_HASHGRID_DET_SCRATCH: {
             if (!meta) { mipsf::set_error("mipsf_buffer_size: buffer %d needs the grid's level table", which); return ~0ull; }
             const uint64_t v = which == MIPSF_SIZE_HASHGRID_BWD_SCRATCH ? mipsf::hashgrid_bwd_scratch_floats(meta, n, (int)a)
+                             : which == MIPSF_SIZE_HASHGRID_DET_SCRATCH ? mipsf::hashgrid_det_scratch_floats(meta, n, (int)a)
                                                                         : mipsf::hashgrid_counter_words(meta);
             if (v == 0) { mipsf::set_error("mipsf_buffer_size: bad level table"); return ~0ull; }
             return v;

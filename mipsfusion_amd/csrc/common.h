@@ -28,6 +28,9 @@ int device_cus();
 // buffer sizes behind mipsf_buffer_size (capi.hip); each is defined next to the kernels that use the buffer
 uint64_t hashgrid_bwd_scratch_floats(const mipsf_grid_meta* meta, uint32_t M, int need_dx);
 uint64_t hashgrid_counter_words(const mipsf_grid_meta* meta);
+uint64_t hashgrid_det_scratch_floats(const mipsf_grid_meta* meta, uint32_t M, int need_dx);
+// the live-tile lists of the backward chain in ascending order, in place (decoder16.hip; MIPSF_WGRAD_DETERMINISTIC)
+int decoder_tile_lists_order(uint32_t* tile_live, uint32_t M, hipStream_t s);
 uint64_t decoder_packed_floats();
 uint64_t decoder_saved_floats(uint32_t M);
 uint64_t decoder_dact_floats(uint32_t M);

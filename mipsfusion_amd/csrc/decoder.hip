@@ -945,6 +945,38 @@ static W to_w(const mipsf_decoder_weights& s) {
 constexpr uint32_t WG_MAX_BLOCKS = 256;
 
 // sum of `nrec` per-block partial records (G_* layout) into the ten gradient tensors; shared with wgrad16.hip
+// MIPSF_WGRAD_DETERMINISTIC (mipsf_decoder_wgrad16): the same sum in ONE order -- a thread per gradient element adds the records
+// in block order and then the total to the gradient (a single writer, a plain fp32 add).  decoder_wgrad_reduce_kernel's eight
+// slices meet in float atomics, whose order follows the schedule.
+__global__ __launch_bounds__(256) void decoder_wgrad_reduce_fixed_kernel(const float* __restrict__ partial, uint32_t nrec,
+                                                                         GradPtrs g) {
+    const int q = blockIdx.x * blockDim.x + threadIdx.x;
+    if (q >= G_TOTAL) return;
+    float a = 0.f;
+    for (uint32_t b = 0; b < nrec; ++b) a += partial[(size_t)b * G_STRIDE + q];
+    const int bounds[11] = {G_W_PTS0, G_B_PTS0, G_W_PTS2, G_B_PTS2, G_W_RGB0, G_B_RGB0,
+                            G_W_SDF0, G_B_SDF0, G_W_SDF2, G_B_SDF2, G_TOTAL};
+#pragma unroll
+    for (int k = 0; k < 10; ++k)
+        if (q >= bounds[k] && q < bounds[k + 1]) {
+            float* p = &g.p[k][q - bounds[k]];
+            *p = *p + a;
+        }
+}
+
+int wgrad_reduce_launch(const float* partial, uint32_t nrec, const mipsf_decoder_grads* grads, hipStream_t s, bool fixed_order) {
+    if (fixed_order) {
+        GradPtrs g;
+        g.p[0] = grads->w_pts0, g.p[1] = grads->b_pts0, g.p[2] = grads->w_pts2, g.p[3] = grads->b_pts2;
+        g.p[4] = grads->w_rgb0, g.p[5] = grads->b_rgb0, g.p[6] = grads->w_sdf0, g.p[7] = grads->b_sdf0;
+        g.p[8] = grads->w_sdf2, g.p[9] = grads->b_sdf2;
+        for (int k = 0; k < 10; ++k) MIPSF_REQUIRE(g.p[k] != nullptr, "null gradient pointer %d", k);
+        hipLaunchKernelGGL(decoder_wgrad_reduce_fixed_kernel, dim3((G_TOTAL + 255) / 256), dim3(256), 0, s, partial, nrec, g);
+        return check_launch("decoder_wgrad_reduce_fixed");
+    }
+    return wgrad_reduce_launch(partial, nrec, grads, s);
+}
+
 int wgrad_reduce_launch(const float* partial, uint32_t nrec, const mipsf_decoder_grads* grads, hipStream_t s) {
     GradPtrs g;
     g.p[0] = grads->w_pts0, g.p[1] = grads->b_pts0, g.p[2] = grads->w_pts2, g.p[3] = grads->b_pts2;

@@ -791,6 +791,57 @@ __device__ __forceinline__ void tl_append(uint32_t* tl, uint32_t n_tiles, uint32
     tl[TL_HEADER + q * tl_cap(n_tiles) + atomicAdd(tl + 64 * q + 32, 1u)] = tile;
 }
 
+// ORDERED LISTS (MIPSF_WGRAD_DETERMINISTIC of mipsf_decoder_wgrad16): tl_append leaves a list in the order its tiles finished, which depends on the
+// schedule, and the weight-gradient kernel deals list positions to its workgroups.  One workgroup per list q puts it in
+// ascending tile order in place.  The candidates of list q are the tiles of the groups g with g % 8 == q, numbered by
+// ordinal o = 8 (g / 8) + member (tile = ((o / 8) * 8 + q) * 8 + o % 8): a bitmap of the ordinals in LDS marks the members,
+// then an ordered compaction (popcounts, a block scan) writes them back over the list once every member has been read.
+constexpr uint32_t TL_ORDER_BLOCK = 1024;
+constexpr uint32_t TL_ORDER_WORDS = 16384;         // 64 KiB of bitmap: 2^19 candidates per list = 2^22 tiles (MIPSF_TILE_ORDER_MAX_M)
+static_assert((uint64_t)TL_ORDER_WORDS * 32u * 8u * 32u >= (uint64_t)MIPSF_TILE_ORDER_MAX_M, "bitmap too small for the limit");
+__global__ __launch_bounds__(TL_ORDER_BLOCK) void tile_lists_order_kernel(uint32_t* __restrict__ tl, uint32_t n_tiles) {
+    __shared__ uint32_t bits[TL_ORDER_WORDS];
+    __shared__ uint32_t wsum[TL_ORDER_BLOCK / MIPSF_WAVE];
+    const uint32_t q = blockIdx.x, t = threadIdx.x, w = t / MIPSF_WAVE, lane = t % MIPSF_WAVE;
+    const uint32_t n_words = (((n_tiles + 63u) / 64u) * 8u + 31u) / 32u;
+    for (uint32_t j = t; j < n_words; j += TL_ORDER_BLOCK) bits[j] = 0u;
+    __syncthreads();
+    uint32_t* list = tl + TL_HEADER + q * tl_cap(n_tiles);
+    const uint32_t count = min(tl[64 * q + 32], tl_cap(n_tiles));
+    for (uint32_t k = t; k < count; k += TL_ORDER_BLOCK) {
+        const uint32_t tile = list[k];
+        const uint32_t o = ((tile >> 6) << 3) | (tile & 7u);
+        if (tile < n_tiles) atomicOr(&bits[o >> 5], 1u << (o & 31u));
+    }
+    __syncthreads();
+    uint32_t base = 0;
+    for (uint32_t j0 = 0; j0 < n_words; j0 += TL_ORDER_BLOCK) {
+        const uint32_t j = j0 + t;
+        const uint32_t b = j < n_words ? bits[j] : 0u;
+        const uint32_t c = (uint32_t)__popc(b);
+        uint32_t incl = c;
+#pragma unroll
+        for (int o = 1; o < MIPSF_WAVE; o <<= 1) {
+            const uint32_t u = __shfl_up(incl, o);
+            if (lane >= (uint32_t)o) incl += u;
+        }
+        if (lane == MIPSF_WAVE - 1) wsum[w] = incl;
+        __syncthreads();
+        uint32_t pos = base + incl - c, total = 0;
+        for (uint32_t v = 0; v < TL_ORDER_BLOCK / MIPSF_WAVE; ++v) {
+            const uint32_t sv = wsum[v];
+            if (v < w) pos += sv;
+            total += sv;
+        }
+        for (uint32_t bb = b; bb != 0u; bb &= bb - 1u) {
+            const uint32_t o = j * 32u + (uint32_t)__ffs(bb) - 1u;
+            list[pos++] = ((o >> 3) * 8u + q) * 8u + (o & 7u);
+        }
+        base += total;
+        __syncthreads();
+    }
+}
+
 template <int LAYOUT, int NP, typename Img>
 __device__ __forceinline__ void decoder16_bwd_tile(const Img bimg, const float* __restrict__ x,
                                                    const float* __restrict__ out, const float* __restrict__ dout,
@@ -1388,3 +1439,16 @@ int mipsf_decoder_bwd_chain16(const mipsf_decoder_chain16_args* a, void* stream)
 }
 
 }  // extern "C"
+
+namespace mipsf {
+// MIPSF_WGRAD_DETERMINISTIC of mipsf_decoder_wgrad16 (wgrad16.hip): the lists in ascending order before the weight gradients
+int decoder_tile_lists_order(uint32_t* tile_live, uint32_t M, hipStream_t s) {
+    if (M == 0) return 0;
+    MIPSF_REQUIRE(tile_live != nullptr, "null tile_live");
+    MIPSF_REQUIRE(M <= MIPSF_TILE_ORDER_MAX_M, "ordered tile lists: M = %u is above their limit of %u samples", M,
+                  (unsigned)MIPSF_TILE_ORDER_MAX_M);
+    const uint32_t n_tiles = (M + 31u) / 32u;
+    hipLaunchKernelGGL(tile_lists_order_kernel, dim3(8), dim3(TL_ORDER_BLOCK), 0, s, tile_live, n_tiles);
+    return check_launch("decoder_tile_lists_order");
+}
+}  // namespace mipsf

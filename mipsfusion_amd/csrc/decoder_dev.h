@@ -199,5 +199,7 @@ __device__ __forceinline__ float load_feat(const float* __restrict__ feat, uint3
 }
 
 int wgrad_reduce_launch(const float* partial, uint32_t nrec, const mipsf_decoder_grads* grads, hipStream_t s);
+// fixed_order: the records summed in block order by one thread per element, no atomics (MIPSF_WGRAD_DETERMINISTIC)
+int wgrad_reduce_launch(const float* partial, uint32_t nrec, const mipsf_decoder_grads* grads, hipStream_t s, bool fixed_order);
 
 }  // namespace mipsf

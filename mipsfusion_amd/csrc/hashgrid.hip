@@ -1239,6 +1239,335 @@ static inline uint32_t grid_blocks(uint32_t M, uint32_t L, uint32_t& nchunk) {
     return 8u * ((L + 7u) / 8u) * nchunk;
 }
 
+// ============================================================== deterministic scatter (MIPSF_HG_DETERMINISTIC)
+// The fixed-order alternative of the LDS-slice scatter above; its contract is written in include/mipsf.h.  A store pass, a
+// sort and per-entry sums (HIP guide, "Scatter / gather / embedding"); integer counts and ranks only, no float atomics:
+//   EMIT    one thread per (sample, level) stores 8 keys -- the global entry index of each corner, DET dead key (= the
+//           number of entries) for a pair whose two gradients are zero -- at position (level * M + i) * 8 + corner
+//   SORT    stable LSD radix sort of the keys, 8-bit digits, only the bits the dead key needs; the value is the position,
+//           so the items of one entry keep the ascending (sample, corner) order.  Per pass: digit counts per block of
+//           DET_TILE items, one scan per digit in block order, stable ranks inside a block from ballots
+//   START   the head of every run of equal keys records its position
+//   PIECES  every piece of MIPSF_HG_DET_PIECE items after an entry's first one is summed in fp64 by one thread.  A piece that
+//           starts at q >= head + PIECE lies inside its entry's run from q - PIECE on, so no other such piece starts in the
+//           same PIECE-aligned window of positions: its sum has the slot q / PIECE
+//   TOTAL   one thread per head sums the first piece, adds the other pieces' sums in order, rounds once and writes dparams
+// Every launch dimension follows from M and the level table.  Contributions are recomputed from the position (locate /
+// corner_weights: the forward's fp32 weight) and the gathered gradient; w * g is exact in fp64.
+constexpr uint32_t DET_BLOCK = 256;                          // = the radix: one digit per thread in the count / scan steps
+constexpr uint32_t DET_PER_THREAD = 16;
+constexpr uint32_t DET_TILE = DET_BLOCK * DET_PER_THREAD;    // items per sort block
+constexpr uint32_t DET_PIECE = MIPSF_HG_DET_PIECE;
+static_assert((DET_PIECE & (DET_PIECE - 1u)) == 0u, "the piece length is a power of two");
+
+template <int LAYOUT>
+__global__ __launch_bounds__(DET_BLOCK) void det_emit_kernel(const float* __restrict__ x, const float* __restrict__ dout,
+                                                             uint32_t* __restrict__ keys, uint32_t M, GridLevels g,
+                                                             uint32_t dead) {
+    const uint32_t level = blockIdx.y;
+    const uint32_t i = blockIdx.x * DET_BLOCK + threadIdx.x;
+    if (i >= M) return;
+    const float2 gy = *reinterpret_cast<const float2*>(dout + feat_index<LAYOUT>(i, level, M, g.n_levels));
+    uint32_t k[8];
+    if (gy.x == 0.f && gy.y == 0.f) {
+#pragma unroll
+        for (int c = 0; c < 8; ++c) k[c] = dead;
+    } else {
+        const uint32_t off = g.offsets[level];
+        const uint32_t size = g.offsets[level + 1] - off;
+        const uint32_t res = g.res[level];
+        const Cell cell = locate(x, i, g.scale[level]);
+        corner_indices(level_mode(res, size), cell, res, size, k);
+#pragma unroll
+        for (int c = 0; c < 8; ++c) k[c] += off;
+    }
+    uint4* dst = reinterpret_cast<uint4*>(keys + ((size_t)level * M + i) * 8);
+    dst[0] = make_uint4(k[0], k[1], k[2], k[3]);
+    dst[1] = make_uint4(k[4], k[5], k[6], k[7]);
+}
+
+// inclusive scan over the block; s[DET_BLOCK - 1] holds the total on return
+__device__ __forceinline__ uint32_t det_block_scan(uint32_t v, uint32_t* s) {
+    s[threadIdx.x] = v;
+    __syncthreads();
+    for (uint32_t o = 1; o < DET_BLOCK; o <<= 1) {
+        const uint32_t t = threadIdx.x >= o ? s[threadIdx.x - o] : 0u;
+        __syncthreads();
+        s[threadIdx.x] += t;
+        __syncthreads();
+    }
+    return s[threadIdx.x];
+}
+
+// cnt[digit * nb + block] = items of the block with that digit
+__global__ __launch_bounds__(DET_BLOCK) void det_count_kernel(const uint32_t* __restrict__ keys, uint32_t* __restrict__ cnt,
+                                                              uint32_t n, uint32_t nb, uint32_t shift) {
+    __shared__ uint32_t h[DET_BLOCK];
+    h[threadIdx.x] = 0u;
+    __syncthreads();
+    const uint32_t base = blockIdx.x * DET_TILE;
+    for (uint32_t r = 0; r < DET_PER_THREAD; ++r) {
+        const uint32_t q = base + r * DET_BLOCK + threadIdx.x;
+        if (q < n) atomicAdd(&h[(keys[q] >> shift) & 255u], 1u);
+    }
+    __syncthreads();
+    cnt[(size_t)threadIdx.x * nb + blockIdx.x] = h[threadIdx.x];
+}
+
+// one block per digit: cnt row -> exclusive prefix in block order, tot[digit] = the row's sum
+__global__ __launch_bounds__(DET_BLOCK) void det_scan_kernel(uint32_t* __restrict__ cnt, uint32_t* __restrict__ tot,
+                                                             uint32_t nb) {
+    __shared__ uint32_t s[DET_BLOCK];
+    uint32_t* row = cnt + (size_t)blockIdx.x * nb;
+    uint32_t carry = 0;
+    for (uint32_t b0 = 0; b0 < nb; b0 += DET_BLOCK) {
+        const uint32_t b = b0 + threadIdx.x;
+        const uint32_t v = b < nb ? row[b] : 0u;
+        const uint32_t incl = det_block_scan(v, s);
+        if (b < nb) row[b] = carry + incl - v;
+        carry += s[DET_BLOCK - 1];
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) tot[blockIdx.x] = carry;
+}
+
+// Stable placement of one block's items.  Round r takes items base + r * DET_BLOCK + t: rounds in order, inside a round the
+// waves in order, inside a wave the lanes in order -- the items' own order.  A lane's rank among the equal digits of its wave
+// comes from 8 ballots; the earlier waves' counts of the round come from LDS.  vin NULL: the value is the position itself.
+__global__ __launch_bounds__(DET_BLOCK) void det_place_kernel(const uint32_t* __restrict__ kin, const uint32_t* __restrict__ vin,
+                                                              uint32_t* __restrict__ kout, uint32_t* __restrict__ vout,
+                                                              const uint32_t* __restrict__ cnt, const uint32_t* __restrict__ tot,
+                                                              uint32_t n, uint32_t nb, uint32_t shift) {
+    constexpr uint32_t NW = DET_BLOCK / MIPSF_WAVE;
+    __shared__ uint32_t next[DET_BLOCK];                // where the block's next item of each digit goes
+    __shared__ uint32_t wc[NW][DET_BLOCK];              // items of each digit per wave in the current round
+    __shared__ uint32_t s[DET_BLOCK];
+    const uint32_t t = threadIdx.x, w = t / MIPSF_WAVE, lane = t % MIPSF_WAVE;
+    {
+        const uint32_t v = tot[t];
+        const uint32_t incl = det_block_scan(v, s);
+        next[t] = incl - v + cnt[(size_t)t * nb + blockIdx.x];
+    }
+    const uint32_t base = blockIdx.x * DET_TILE;
+    for (uint32_t r = 0; r < DET_PER_THREAD; ++r) {
+        for (uint32_t j = lane; j < DET_BLOCK; j += MIPSF_WAVE) wc[w][j] = 0u;
+        const uint32_t q = base + r * DET_BLOCK + t;
+        const bool ok = q < n;
+        const uint32_t key = ok ? kin[q] : 0u;
+        const uint32_t d = (key >> shift) & 255u;
+        uint64_t peers = __ballot(ok);
+#pragma unroll
+        for (int b = 0; b < 8; ++b) {
+            const uint64_t m = __ballot((d >> b) & 1u);
+            peers &= ((d >> b) & 1u) ? m : ~m;
+        }
+        const uint32_t below = __builtin_amdgcn_mbcnt_hi((uint32_t)(peers >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)peers, 0u));
+        __syncthreads();
+        if (ok && below == 0u) wc[w][d] = (uint32_t)__popcll(peers);
+        __syncthreads();
+        if (ok) {
+            uint32_t pos = next[d] + below;
+            for (uint32_t v = 0; v < w; ++v) pos += wc[v][d];
+            kout[pos] = key;
+            vout[pos] = vin ? vin[q] : q;
+        }
+        __syncthreads();
+        uint32_t add = 0;
+#pragma unroll
+        for (uint32_t v = 0; v < NW; ++v) add += wc[v][t];
+        next[t] += add;
+        __syncthreads();
+    }
+}
+
+__global__ __launch_bounds__(DET_BLOCK) void det_start_kernel(const uint32_t* __restrict__ keys, uint32_t* __restrict__ start,
+                                                              uint32_t n, uint32_t dead) {
+    const uint32_t q = blockIdx.x * DET_BLOCK + threadIdx.x;
+    if (q >= n) return;
+    const uint32_t k = keys[q];
+    if (k != dead && (q == 0u || keys[q - 1] != k)) start[k] = q;
+}
+
+// fp64 sum, left to right from +0, of the items q, q + 1, ... of entry `key` (at most DET_PIECE of them).  Four items per
+// step so that their gathers are in flight together; the items of an entry are a run, so the matching ones are a prefix.
+template <int LAYOUT>
+__device__ __forceinline__ double2 det_piece(const float* __restrict__ x, const float* __restrict__ dout,
+                                             const uint32_t* __restrict__ keys, const uint32_t* __restrict__ vals, uint32_t q,
+                                             uint32_t key, uint32_t n, uint32_t M, const GridLevels& g) {
+    double s0 = 0.0, s1 = 0.0;
+    const uint32_t end = n - q < DET_PIECE ? n : q + DET_PIECE;
+    for (uint32_t p0 = q; p0 < end; p0 += 4) {
+        bool same[4];
+        double v0[4], v1[4];
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            const uint32_t p = p0 + j;
+            same[j] = p < end && keys[p] == key;
+            const uint32_t pos = p < end ? vals[p] : 0u;
+            const uint32_t pair = pos >> 3, c = pos & 7u;
+            const uint32_t level = pair / M, i = pair - level * M;
+            const Cell cell = locate(x, i, g.scale[level]);
+            float w[8];
+            corner_weights(cell, w);
+            float wc = w[0];
+#pragma unroll
+            for (uint32_t k = 1; k < 8; ++k) wc = c == k ? w[k] : wc;
+            const float2 gy = *reinterpret_cast<const float2*>(dout + feat_index<LAYOUT>(i, level, M, g.n_levels));
+            v0[j] = (double)wc * (double)gy.x;
+            v1[j] = (double)wc * (double)gy.y;
+        }
+        bool more = true;
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            more = more && same[j];
+            if (more) s0 += v0[j], s1 += v1[j];
+        }
+        if (!more) break;
+    }
+    return make_double2(s0, s1);
+}
+
+template <int LAYOUT>
+__global__ __launch_bounds__(DET_BLOCK) void det_pieces_kernel(const float* __restrict__ x, const float* __restrict__ dout,
+                                                               const uint32_t* __restrict__ keys,
+                                                               const uint32_t* __restrict__ vals,
+                                                               const uint32_t* __restrict__ start, double2* __restrict__ psum,
+                                                               uint32_t n, uint32_t M, GridLevels g, uint32_t dead) {
+    const uint32_t q = blockIdx.x * DET_BLOCK + threadIdx.x;
+    if (q >= n) return;
+    const uint32_t k = keys[q];
+    if (k == dead) return;
+    const uint32_t r = q - start[k];
+    if (r == 0u || (r & (DET_PIECE - 1u)) != 0u) return;
+    psum[q / DET_PIECE] = det_piece<LAYOUT>(x, dout, keys, vals, q, k, n, M, g);
+}
+
+template <int LAYOUT>
+__global__ __launch_bounds__(DET_BLOCK) void det_total_kernel(const float* __restrict__ x, const float* __restrict__ dout,
+                                                              const uint32_t* __restrict__ keys,
+                                                              const uint32_t* __restrict__ vals,
+                                                              const double2* __restrict__ psum, float* __restrict__ dparams,
+                                                              uint32_t n, uint32_t M, GridLevels g, uint32_t dead,
+                                                              uint32_t fresh) {
+    const uint32_t q = blockIdx.x * DET_BLOCK + threadIdx.x;
+    if (q >= n) return;
+    const uint32_t k = keys[q];
+    if (k == dead || (q > 0u && keys[q - 1] == k)) return;
+    const double2 p = det_piece<LAYOUT>(x, dout, keys, vals, q, k, n, M, g);
+    double s0 = 0.0, s1 = 0.0;
+    s0 += p.x, s1 += p.y;
+    for (uint32_t qj = q + DET_PIECE; qj < n && qj > q && keys[qj] == k; qj += DET_PIECE) {
+        const double2 pj = psum[qj / DET_PIECE];
+        s0 += pj.x, s1 += pj.y;
+    }
+    float2* d = reinterpret_cast<float2*>(dparams) + k;
+    float2 v = make_float2((float)s0, (float)s1);
+    if (!fresh) {
+        const float2 old = *d;
+        v = make_float2(old.x + v.x, old.y + v.y);
+    }
+    *d = v;
+}
+
+// scratch of the deterministic path, in 32-bit words: piece sums | keys x 2 | values x 2 | digit counts | digit totals |
+// entry starts | (dx) per-level partials of dL/dx
+struct DetPlan {
+    uint64_t n;                 // items = 8 L M
+    uint32_t nb, dead, passes;
+    uint64_t o_keys[2], o_vals[2], o_cnt, o_tot, o_start, o_dxl, w_end;
+};
+
+static DetPlan det_plan(const GridLevels& g, uint32_t M) {
+    DetPlan p;
+    p.n = 8ull * g.n_levels * M;
+    p.nb = (uint32_t)((p.n + DET_TILE - 1) / DET_TILE);
+    p.dead = g.offsets[g.n_levels];
+    uint32_t bits = 0;
+    while (bits < 32u && (p.dead >> bits) != 0u) ++bits;
+    p.passes = (bits + 7u) / 8u;
+    uint64_t o = 4ull * ((p.n + DET_PIECE - 1) / DET_PIECE);
+    for (int k = 0; k < 2; ++k) p.o_keys[k] = o, o += (p.n + 3) / 4 * 4;
+    for (int k = 0; k < 2; ++k) p.o_vals[k] = o, o += (p.n + 3) / 4 * 4;
+    p.o_cnt = o, o += 256ull * p.nb;
+    p.o_tot = o, o += 256;
+    p.o_start = o, o += p.dead;
+    p.o_dxl = (o + 15) / 16 * 16;
+    p.w_end = p.o_dxl;
+    return p;
+}
+
+uint64_t hashgrid_det_scratch_floats(const mipsf_grid_meta* meta, uint32_t M, int need_dx) {
+    GridLevels g;
+    if (to_levels(meta, g)) return 0;
+    const DetPlan p = det_plan(g, M);
+    return p.w_end + (need_dx ? (uint64_t)g.n_levels * M * 3 : 0) + 64;
+}
+
+static int hashgrid_bwd_det(const float* x, const float* params, const float* dout, float* dparams, float* dx, float* scratch,
+                            uint32_t M, const mipsf_grid_meta* meta, int layout, bool fresh, void* stream) {
+    GridLevels g;
+    if (int rc = to_levels(meta, g)) return rc;
+    if (M == 0) return 0;
+    MIPSF_REQUIRE(x && params && dout && scratch, "null pointer");
+    MIPSF_REQUIRE(dparams || dx, "nothing to compute: dparams and dx are both null");
+    MIPSF_REQUIRE(layout == MIPSF_FEAT_AOS || layout == MIPSF_FEAT_LEVEL_MAJOR, "bad layout %d", layout);
+    MIPSF_REQUIRE(8ull * g.n_levels * M <= MIPSF_HG_DET_MAX_ITEMS,
+                  "deterministic scatter: 8 x %u levels x M = %u is above its limit of 2^31 items (M <= %u)", g.n_levels, M,
+                  (unsigned)(MIPSF_HG_DET_MAX_ITEMS / (8ull * g.n_levels)));
+    const DetPlan p = det_plan(g, M);
+    hipStream_t s = (hipStream_t)stream;
+    uint32_t* ws = reinterpret_cast<uint32_t*>(scratch);
+    if (dparams) {
+        const uint32_t n = (uint32_t)p.n, nb = p.nb;
+        uint32_t *keys[2] = {ws + p.o_keys[0], ws + p.o_keys[1]}, *vals[2] = {ws + p.o_vals[0], ws + p.o_vals[1]};
+        uint32_t *cnt = ws + p.o_cnt, *tot = ws + p.o_tot, *start = ws + p.o_start;
+        double2* psum = reinterpret_cast<double2*>(scratch);
+        const dim3 eg((M + DET_BLOCK - 1) / DET_BLOCK, g.n_levels);
+        if (layout == MIPSF_FEAT_AOS)
+            hipLaunchKernelGGL(det_emit_kernel<MIPSF_FEAT_AOS>, eg, dim3(DET_BLOCK), 0, s, x, dout, keys[0], M, g, p.dead);
+        else
+            hipLaunchKernelGGL(det_emit_kernel<MIPSF_FEAT_LEVEL_MAJOR>, eg, dim3(DET_BLOCK), 0, s, x, dout, keys[0], M, g, p.dead);
+        if (int e = check_launch("hashgrid_det_emit")) return e;
+        for (uint32_t pass = 0; pass < p.passes; ++pass) {
+            const uint32_t a = pass & 1u, shift = 8u * pass;
+            hipLaunchKernelGGL(det_count_kernel, dim3(nb), dim3(DET_BLOCK), 0, s, keys[a], cnt, n, nb, shift);
+            hipLaunchKernelGGL(det_scan_kernel, dim3(256), dim3(DET_BLOCK), 0, s, cnt, tot, nb);
+            hipLaunchKernelGGL(det_place_kernel, dim3(nb), dim3(DET_BLOCK), 0, s, keys[a], pass ? vals[a] : nullptr, keys[a ^ 1u],
+                               vals[a ^ 1u], cnt, tot, n, nb, shift);
+            if (int e = check_launch("hashgrid_det_sort")) return e;
+        }
+        const uint32_t* sk = keys[p.passes & 1u];
+        const uint32_t* sv = vals[p.passes & 1u];
+        const uint32_t tb = (uint32_t)((p.n + DET_BLOCK - 1) / DET_BLOCK);
+        hipLaunchKernelGGL(det_start_kernel, dim3(tb), dim3(DET_BLOCK), 0, s, sk, start, n, p.dead);
+#define DET_SUMS(LAY)                                                                                                    \
+    do {                                                                                                                 \
+        hipLaunchKernelGGL(det_pieces_kernel<LAY>, dim3(tb), dim3(DET_BLOCK), 0, s, x, dout, sk, sv, start, psum, n, M, g, \
+                           p.dead);                                                                                      \
+        hipLaunchKernelGGL(det_total_kernel<LAY>, dim3(tb), dim3(DET_BLOCK), 0, s, x, dout, sk, sv, psum, dparams, n, M, g, \
+                           p.dead, fresh ? 1u : 0u);                                                                     \
+    } while (0)
+        if (layout == MIPSF_FEAT_AOS) DET_SUMS(MIPSF_FEAT_AOS); else DET_SUMS(MIPSF_FEAT_LEVEL_MAJOR);
+#undef DET_SUMS
+        if (int e = check_launch("hashgrid_det_sums")) return e;
+    }
+    if (dx) {      // the fast path's dL/dx kernels (already fixed-order: per-level partials summed in level order)
+        float* dxl = scratch + p.o_dxl;
+        uint32_t nchunk;
+        const uint32_t nb = grid_blocks(M, g.n_levels, nchunk);
+        const float2* table = reinterpret_cast<const float2*>(params);
+        if (layout == MIPSF_FEAT_AOS)
+            hipLaunchKernelGGL(hashgrid_dx_kernel<MIPSF_FEAT_AOS>, dim3(nb), dim3(HG_BLOCK), 0, s, x, table, dout, dxl, M, g, nchunk);
+        else
+            hipLaunchKernelGGL(hashgrid_dx_kernel<MIPSF_FEAT_LEVEL_MAJOR>, dim3(nb), dim3(HG_BLOCK), 0, s, x, table, dout, dxl, M, g, nchunk);
+        if (int e = check_launch("hashgrid_dx")) return e;
+        const uint64_t n3 = (uint64_t)M * 3;
+        hipLaunchKernelGGL(hashgrid_dx_reduce_kernel, dim3((uint32_t)((n3 + 255) / 256)), dim3(256), 0, s, dxl, dx, n3, g.n_levels);
+        if (int e = check_launch("hashgrid_dx_reduce")) return e;
+    }
+    return 0;
+}
+
 }  // namespace mipsf
 
 using namespace mipsf;
@@ -1441,7 +1770,14 @@ int mipsf_hashgrid_bwd(const mipsf_hashgrid_bwd_args* a, void* stream) {
     MIPSF_REQUIRE(a != nullptr, "null argument block");
     MIPSF_REQUIRE(a->struct_size == sizeof(mipsf_hashgrid_bwd_args), "mipsf_hashgrid_bwd_args: struct_size %u, this library expects %u",
                   a->struct_size, (unsigned)sizeof(mipsf_hashgrid_bwd_args));
-    MIPSF_REQUIRE((a->flags & ~(uint32_t)(MIPSF_HG_DPARAMS_ZERO | MIPSF_HG_ROUTED)) == 0u, "unknown flags 0x%x", a->flags);
+    MIPSF_REQUIRE((a->flags & ~(uint32_t)(MIPSF_HG_DPARAMS_ZERO | MIPSF_HG_ROUTED | MIPSF_HG_DETERMINISTIC)) == 0u,
+                  "unknown flags 0x%x", a->flags);
+    if (a->flags & MIPSF_HG_DETERMINISTIC) {
+        MIPSF_REQUIRE(!(a->flags & MIPSF_HG_ROUTED), "MIPSF_HG_DETERMINISTIC with MIPSF_HG_ROUTED: the routed scratch belongs to "
+                      "the fast scatter; the deterministic path takes its own scratch (MIPSF_SIZE_HASHGRID_DET_SCRATCH)");
+        return hashgrid_bwd_det(a->x, a->params, a->dout, a->dparams, a->dx, a->scratch, a->M, a->meta, a->feat_layout,
+                                (a->flags & MIPSF_HG_DPARAMS_ZERO) != 0u, stream);
+    }
     return hashgrid_bwd_impl(a->x, a->params, a->dout, a->dparams, a->dx, a->scratch, a->counters, a->M, a->meta, a->feat_layout,
                              (a->flags & MIPSF_HG_ROUTED) != 0u, stream, (a->flags & MIPSF_HG_DPARAMS_ZERO) != 0u);
 }

@@ -2109,7 +2109,7 @@ extern "C" int mipsf_decoder_wgrad16(const mipsf_decoder_wgrad16_args* a, void* 
                   "packed16 holds %u floats, arithmetic %d needs %u: packed for the other family?", a->packed16_floats, arithmetic,
                   (unsigned)decoder_packed16_floats(arithmetic));
     if (M == 0) return 0;
-    MIPSF_REQUIRE((flags & ~(uint32_t)MIPSF_WGRAD_LEAN_DACT) == 0u, "unknown flags 0x%x", flags);
+    MIPSF_REQUIRE((flags & ~(uint32_t)(MIPSF_WGRAD_LEAN_DACT | MIPSF_WGRAD_DETERMINISTIC)) == 0u, "unknown flags 0x%x", flags);
     const uint32_t lean_dact = (flags & MIPSF_WGRAD_LEAN_DACT) ? 1u : 0u;
     MIPSF_REQUIRE(!lean_dact || (packed16 != nullptr && (arithmetic == MIPSF_PREC_F16X3 || arithmetic == MIPSF_PREC_BF16X6) && W16_EXCHANGE),
                   "the lean gradient record is read by the f16x3 / bf16x6 kernel with packed16 only");
@@ -2121,6 +2121,9 @@ extern "C" int mipsf_decoder_wgrad16(const mipsf_decoder_wgrad16_args* a, void* 
                   "arithmetic must be f16x3, bf16x6 or bf16x3");
     MIPSF_REQUIRE(M < (1u << 25), "M = %u: the grid features are addressed through one 4 GB buffer resource", M);
     hipStream_t s = (hipStream_t)stream;
+    const bool det = (flags & MIPSF_WGRAD_DETERMINISTIC) != 0u;
+    if (det && tile_live)         // (the caller's buffer: the lists are reordered in place, members and counts kept)
+        if (int e = decoder_tile_lists_order(const_cast<uint32_t*>(tile_live), M, s)) return e;
     const uint32_t n_tiles = (uint32_t)(((uint64_t)M + 31) / 32);
     const uint64_t n_bt = ((uint64_t)M + 127) / 128;
     const float* dsmall = dact + n_bt * 4 * ACT_TILE_FLOATS;
@@ -2138,5 +2141,5 @@ extern "C" int mipsf_decoder_wgrad16(const mipsf_decoder_wgrad16_args* a, void* 
 #undef W16_L
 #undef W16
     if (int e = check_launch("decoder_wgrad16")) return e;
-    return wgrad_reduce_launch(partial, blocks, grads, s);
+    return wgrad_reduce_launch(partial, blocks, grads, s, det);
 }

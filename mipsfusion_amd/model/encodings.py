@@ -20,6 +20,10 @@ class Encoding(torch.nn.Module):
         self.seed = seed
         self.dtype = dtype
         self.loss_scale = 1.0
+        # extension (tcnn's backward adds the grid gradient with float atomics): the hash grid's parameter gradient in a fixed
+        # order (MIPSF_HG_DETERMINISTIC).  None follows torch.are_deterministic_algorithms_enabled() when the backward runs;
+        # True / False force it
+        self.deterministic = None
         self.otype = encoding_config["otype"].lower()
         if self.otype == "hashgrid":
             if n_input_dims != 3:
@@ -49,6 +53,7 @@ class Encoding(torch.nn.Module):
         # ctypes level table is rebuilt instead of copied (copy.deepcopy(model), InactiveMap.py:67,81,107)
         new = Encoding(self.n_input_dims, self.encoding_config, self.dtype, self.seed)
         new.params = torch.nn.Parameter(self.params.detach().clone(), requires_grad=self.params.requires_grad)
+        new.deterministic = self.deterministic
         new.train(self.training)
         memo[id(self)] = new
         return new
@@ -58,7 +63,7 @@ class Encoding(torch.nn.Module):
             raise RuntimeError("mipsfusion_amd encodings run on the GPU only (no CPU fallback)")
         x = x.to(torch.float)
         if self.otype == "hashgrid":
-            return ops.HashGridFn.apply(x, self.params, self.meta)
+            return ops.HashGridFn.apply(x, self.params, self.meta, self.deterministic)
         if self.otype == "frequency":
             return ops.FrequencyFn.apply(x, self.n_frequencies)
         return x * 1.0

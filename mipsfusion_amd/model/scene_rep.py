@@ -85,7 +85,8 @@ class _QueryFn(torch.autograd.Function):
         # the routing half of the grid's parameter-gradient scatter only needs the points: it runs on a second stream
         # next to this forward pass (joined before the forward returns, so nothing is left dangling if no backward follows)
         routed = None
-        if ctx.needs_input_grad[2] and owner.route_ahead and M >= _ROUTE_AHEAD_MIN_M:
+        # (not in deterministic mode: that scatter has no routing half)
+        if ctx.needs_input_grad[2] and owner.route_ahead and M >= _ROUTE_AHEAD_MIN_M and not ops.resolve_deterministic(owner.deterministic):
             routed = ops.hashgrid_route_ahead(xn, meta)
         if ctx.needs_input_grad[0]:
             feat, jac = ops.hashgrid_fwd(xn, grid_params.detach(), meta, FEAT_LEVEL_MAJOR, with_jac=True)
@@ -136,6 +137,7 @@ class _QueryFn(torch.autograd.Function):
         need_x = ctx.needs_input_grad[0]
         if ctx.tile_live is not None:
             saved.mipsf_tile_live = ctx.tile_live
+        det = ops.resolve_deterministic(ctx.owner.deterministic)
         direct = ctx.owner.accumulate_param_grads_in_place and all(
             p.is_leaf and not p._backward_hooks for p in (grid_params, *weights))
         # frozen parameters (requires_grad False, e.g. the map during tracking) skip their kernels entirely
@@ -152,7 +154,7 @@ class _QueryFn(torch.autograd.Function):
         dfeat, dx, _, tiles = ops.decoder_bwd(packed, feat, FEAT_LEVEL_MAJOR, xn, None, out, ops._f32c(dout), saved, grads,
                                               ctx.M, precision=ctx.prec, packed16=packed if ctx.prec != "f32" else None,
                                               wgrad_precision=("stream_" + ctx.prec) if ctx.lean else ctx.owner.wgrad_precision,
-                                              recompute_h1=ctx.lean, return_tiles=True)
+                                              recompute_h1=ctx.lean, return_tiles=True, deterministic=det)
         dparams = None
         fresh_grad = False
         if need_g:
@@ -166,7 +168,7 @@ class _QueryFn(torch.autograd.Function):
         if need_g:
             # (a fresh zeros tensor, or the caller's word that the optimiser left .grad zero: slices are stored, not added)
             ops.hashgrid_bwd(xn, grid_params.detach(), dfeat, dparams, ctx.meta, FEAT_LEVEL_MAJOR, None, routed=ctx.routed,
-                             dparams_zero=(not direct) or fresh_grad or ctx.owner.grid_grad_is_zero_at_backward)
+                             dparams_zero=(not direct) or fresh_grad or ctx.owner.grid_grad_is_zero_at_backward, deterministic=det)
             ctx.routed = None
         if need_x:
             ops.hashgrid_dx_from_jac(jac, dfeat, dx, ctx.meta, FEAT_LEVEL_MAJOR, tiles=tiles)   # (dfeat is untouched since the chain wrote it)
@@ -248,6 +250,12 @@ class JointEncoding(nn.Module):
         # / the captured loops) -- the grid scatter then stores its slices instead of adding to the old values.  Wrong
         # gradients if the promise is broken (several backward passes accumulated before a step): off by default.
         self.grid_grad_is_zero_at_backward = False
+        # extension (tcnn's own backward adds the grid gradient with float atomics): deterministic training -- the grid scatter
+        # in a fixed order (MIPSF_HG_DETERMINISTIC) and the decoder's live-tile lists ordered before the weight-gradient
+        # kernel, so the same inputs give the same bits on every run, stream and graph replay (on one device, one build).
+        # None follows torch.are_deterministic_algorithms_enabled(), read when the backward runs (at capture time for a
+        # graph); True / False force it.  Costs time: DESIGN.md 4.11
+        self.deterministic = None
         # arithmetic of the decoder (csrc/decoder16.hip, csrc/decoder.hip):
         #   "bf16x6" (default) every fp32 operand -- weight and activation -- carried EXACTLY as three bf16 pieces, a product =
         #           six MFMAs on the bf16 matrix cores, fp32 accumulate: the arithmetic of the reference's fp32 nn.Linear
@@ -357,6 +365,7 @@ class JointEncoding(nn.Module):
         new.wgrad_precision = self.wgrad_precision
         new.lean_record = self.lean_record
         new.route_ahead = self.route_ahead
+        new.deterministic = self.deterministic
         new._frozen_pack = None
         new.train(self.training)
         return new

@@ -178,20 +178,33 @@ def _scatter_counters(device, meta):
 LEAN_DACT = not bool(os.environ.get("MIPSF_FULL_DACT"))
 HG_DPARAMS_ZERO = 1     # include/mipsf.h MIPSF_HG_DPARAMS_ZERO
 HG_ROUTED = 2           # MIPSF_HG_ROUTED
+HG_DETERMINISTIC = 4    # MIPSF_HG_DETERMINISTIC
 _HG_IGNORE_ZERO_HINT = bool(os.environ.get("MIPSF_HG_IGNORE_ZERO_HINT"))     # experiments: always read-modify-write
 
 
 def hashgrid_bwd(x, params, dout, dparams, meta, layout=FEAT_AOS, dx: Optional[torch.Tensor] = None, routed=None,
-                 dparams_zero=False):
+                 dparams_zero=False, deterministic=False):
     """dparams (and dx when given) are accumulated into.  routed: (scratch, event) of hashgrid_route_ahead for this x.
     dparams_zero: the caller vouches that dparams is all zero now (a fresh torch.zeros, a gradient buffer the optimiser
-    cleared): the table slices are stored instead of read-modify-written."""
+    cleared): the table slices are stored instead of read-modify-written.
+    deterministic: the fixed-order scatter (MIPSF_HG_DETERMINISTIC, contract in include/mipsf.h): the same inputs give the
+    same bits on every run, stream and graph replay.  A `routed` pair is then only waited for; its scratch is not used."""
     M = x.shape[0]
     if PROFILE is not None:
         global _LAST_SCATTER_DOUT
         _LAST_SCATTER_DOUT = dout
     a = _lib.HashgridBwdArgs.new(M=M, x=dptr(x), params=dptr(params), dout=dptr(dout), dparams=dptr(dparams),
                                  meta=C.pointer(meta), feat_layout=layout)
+    if deterministic:
+        if routed is not None:
+            torch.cuda.current_stream(x.device).wait_event(routed[1])     # (its scratch may be reused only after the route)
+        n = _lib.buffer_size(_lib.SIZE_HASHGRID_DET_SCRATCH, M, 1 if dx is not None else 0, 0, meta)
+        scratch = torch.empty(n, dtype=torch.float32, device=x.device)
+        a.dx, a.scratch = dptr(dx), dptr(scratch)
+        a.flags = HG_DETERMINISTIC | (HG_DPARAMS_ZERO if (dparams_zero and not _HG_IGNORE_ZERO_HINT) else 0)
+        with _timed("hashgrid_bwd"):
+            check(lib().mipsf_hashgrid_bwd(C.byref(a), stream_ptr()), "hashgrid_bwd (deterministic)")
+        return
     if routed is not None and dx is None and dparams is not None:
         scratch, ev = routed
         torch.cuda.current_stream(x.device).wait_event(ev)
@@ -216,13 +229,21 @@ def hashgrid_indices(x, meta) -> torch.Tensor:
     return idx
 
 
+def resolve_deterministic(flag) -> bool:
+    """The `deterministic` attribute of the modules: None follows torch.are_deterministic_algorithms_enabled() (read when
+    the backward runs, i.e. at capture time for a graph), True / False force it."""
+    return torch.are_deterministic_algorithms_enabled() if flag is None else bool(flag)
+
+
 class HashGridFn(torch.autograd.Function):
-    """tcnn.Encoding(HashGrid) forward/backward (dense fp32 parameter gradient, dL/dx)."""
+    """tcnn.Encoding(HashGrid) forward/backward (dense fp32 parameter gradient, dL/dx).  deterministic: see
+    resolve_deterministic."""
 
     @staticmethod
-    def forward(ctx, x, params, meta):
+    def forward(ctx, x, params, meta, deterministic=None):
         x = _f32c(x)
         ctx.meta = meta
+        ctx.deterministic = deterministic
         if ctx.needs_input_grad[0]:
             out, jac = hashgrid_fwd(x, params.detach(), meta, FEAT_AOS, with_jac=True)
             ctx.save_for_backward(x, params, jac)
@@ -237,10 +258,11 @@ class HashGridFn(torch.autograd.Function):
         dparams = torch.zeros_like(params) if ctx.needs_input_grad[1] else None
         dx = torch.zeros_like(x) if ctx.needs_input_grad[0] else None
         if dparams is not None:
-            hashgrid_bwd(x, params.detach(), dout, dparams, ctx.meta, FEAT_AOS, None, dparams_zero=True)
+            hashgrid_bwd(x, params.detach(), dout, dparams, ctx.meta, FEAT_AOS, None, dparams_zero=True,
+                         deterministic=resolve_deterministic(ctx.deterministic))
         if dx is not None:
             hashgrid_dx_from_jac(jac[0], dout, dx, ctx.meta, FEAT_AOS)
-        return dx, dparams, None
+        return dx, dparams, None, None
 
 
 # ------------------------------------------------------------------------------ frequency
@@ -368,7 +390,8 @@ def decoder_fwd(packed, feat, layout, x, embed_pos, M, save, precision: str = "f
 
 
 def decoder_bwd(packed, feat, layout, x, embed_pos, out, dout, saved, grads, M, precision: str = "f32", packed16=None,
-                wgrad_precision: str = "auto", recompute_h1: bool = False, return_tiles: bool = False):
+                wgrad_precision: str = "auto", recompute_h1: bool = False, return_tiles: bool = False,
+                deterministic: bool = False):
     """grads: 10 tensors in DECODER_PARAM_ORDER, accumulated into, or None (frozen decoder: the weight-gradient
     GEMMs are skipped).  -> (dfeat, dx, dembed_pos|None).  precision "f16x3": the activation-gradient chain runs on
     the f16 matrix cores with hi/lo split operands (packed16, in-kernel positional encoding); it leaves the same `dact`
@@ -385,7 +408,11 @@ def decoder_bwd(packed, feat, layout, x, embed_pos, out, dout, saved, grads, M, 
     tiles whose incoming gradient is zero throughout -- the ray tails behind the truncation band, a third of a mapping
     batch -- are flagged by the chain, get zero dfeat / dx, and are never touched by the weight-gradient kernel.
     return_tiles: a 4th return value, the chain's live-tile lists (or None when no short cut was taken), for
-    ``hashgrid_dx_from_jac(..., tiles=)``."""
+    ``hashgrid_dx_from_jac(..., tiles=)``.
+    deterministic: the streaming weight-gradient kernel runs with MIPSF_WGRAD_DETERMINISTIC: the live-tile lists are put in
+    ascending order before it reads them (the chain fills them in the order its tiles finish, and the kernel's sums follow
+    the list order) and its per-workgroup records are summed in a fixed order (the default reduce meets in float atomics).
+    The fp32 weight-gradient kernels ("f32", "bf16x3") are refused."""
     if wgrad_precision == "auto":
         wgrad_precision = ("stream_" + precision) if (precision in SPLIT_PRECISIONS and embed_pos is None) else "f32"
     if getattr(saved, "mipsf_masks_only", False) and grads is not None:
@@ -448,12 +475,17 @@ def decoder_bwd(packed, feat, layout, x, embed_pos, out, dout, saved, grads, M, 
             a = _lib.DecoderWgrad16Args.new(M=M, packed16=dptr(packed16) if recompute_h1 else None, feat=dptr(feat), x=dptr(x),
                                             saved=dptr(saved), dact=dptr(dact), tile_live=dptr(tile_live, torch.int32),
                                             grads=C.pointer(st), partial=dptr(partial), feat_layout=layout, arithmetic=arith,
-                                            flags=1 if lean_dact else 0, packed16_floats=packed16.numel() if recompute_h1 else 0)
+                                            flags=(_lib.WGRAD_LEAN_DACT if lean_dact else 0)
+                                            | (_lib.WGRAD_DETERMINISTIC if deterministic else 0),
+                                            packed16_floats=packed16.numel() if recompute_h1 else 0)
             with _timed("decoder_wgrad"):
                 check(lib().mipsf_decoder_wgrad16(C.byref(a), stream_ptr()), "decoder_wgrad16")
             return (dfeat, dx, dpe, tile_live) if return_tiles else (dfeat, dx, dpe)
         if recompute_h1:
             raise RuntimeError("recompute_h1 needs wgrad_precision 'stream_f16x3'")
+        if deterministic:
+            raise RuntimeError("deterministic training needs the streaming weight-gradient kernel (decoder_precision 'bf16x6' / "
+                               "'f16x3', wgrad_precision 'auto' or 'stream_*'): the fp32 kernel's reduce adds in float atomics")
         with _timed("decoder_wgrad"):
             wprec = _lib.PREC[wgrad_precision]
             check(lib().mipsf_decoder_wgrad(dptr(feat), layout, dptr(x), dptr(embed_pos), pe_mode, dptr(saved),

@@ -443,7 +443,7 @@ class GraphedSequence:
 
     def __init__(self, cfg, dev, frames, kf_every=15, sampler="reference", first_iters=None, stream=None,
                  lookahead=None, graph_ro=True, gate_producer=True, ro_precision=None, schedule=None, decoder_precision=None,
-                 device_handover=None):
+                 device_handover=None, deterministic=None):
         """lookahead: how many frames the sample producer runs ahead of the GPU (default: ``map_every``, one whole
         mapping period -- a BA round needs ~40 ms of serial generator work, a frame without BA ~4 ms, so the work only
         evens out over a period; the reference's own DataLoader prefetches 8 frames, mipsfusion.py:672).
@@ -451,7 +451,9 @@ class GraphedSequence:
         schedule: {frame: ("new",) | ("back", submap)} at keyframe frames (see the class docstring).
         decoder_precision: arithmetic of the model's decoder (default: JointEncoding's own default, "bf16x6" = the reference's
         fp32 arithmetic; "f16x3" = the fast mode).  ro_precision: arithmetic of the RandomOptimizer rounds (default: the
-        model's; "f16" = the opt-in plain-f16 rounds of BASELINE config 5, pose within 1e-3 of the reference's)."""
+        model's; "f16" = the opt-in plain-f16 rounds of BASELINE config 5, pose within 1e-3 of the reference's).
+        deterministic: JointEncoding.deterministic of the model (default None: follow torch.are_deterministic_algorithms_enabled()
+        at capture time); True = fixed-order mapping backward, the same run gives the same trajectory bit for bit."""
         from .RandomOptimizer import RandomOptimizer
         from .graph import GraphedSteps, work_stream
         from .model import JointEncoding
@@ -483,6 +485,7 @@ class GraphedSequence:
         self.model = JointEncoding(cfg, bb, nf).to(dev).train()
         if decoder_precision is not None:
             self.model.decoder_precision = decoder_precision
+        self.model.deterministic = deterministic
         self.model.accumulate_param_grads_in_place = True
         # map_accum_step 1, map_wait_step 0 is what every shipped configuration of the reference uses (mipsfusion.py:330-335):
         # the captured loops run ONE backward per map step and the optimiser kernel clears the gradients (the shipped values);
