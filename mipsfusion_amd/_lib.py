@@ -174,6 +174,21 @@ SIGNATURES = {
 }
 
 
+# include/mipsf_mesh.h (the mesh extractor; a header of its own, so a table of its own)
+SIZE_MCUBES_OFFSET_WORDS, SIZE_MCUBES_WELD_SLOTS, SIZE_MCUBES_WELD_WORDS = 20, 21, 22
+MCUBES_BLOCK_CELLS = 4096
+McubesArgs = _args("McubesArgs", [("X", _CU), ("Y", _CU), ("Z", _CU), ("isovalue", C.c_float), ("truncation", C.c_float),
+                                  ("volume", _VP), ("cases", _VP), ("block_offsets", _VP), ("soup", _VP), ("cell_ids", _VP),
+                                  ("capacity_tris", _CU)])
+McubesWeldArgs = _args("McubesWeldArgs", [("T", _CU), ("soup", _VP), ("scratch", _VP), ("vertices", _VP), ("faces", _VP),
+                                          ("counts", _VP), ("max_rounds", _CU)])
+MESH_SIGNATURES = {
+    "mipsf_mcubes_count": (_I, [C.POINTER(McubesArgs), _P]),
+    "mipsf_mcubes_emit": (_I, [C.POINTER(McubesArgs), _P]),
+    "mipsf_mcubes_weld": (_I, [C.POINTER(McubesWeldArgs), _P]),
+}
+
+
 def buffer_size(which: int, n: int = 0, a: int = 0, b: int = 0, meta=None) -> int:
     """mipsf_buffer_size: elements of a scratch / record buffer (SIZE_* above)."""
     v = lib().mipsf_buffer_size(which, n, a, b, C.byref(meta) if meta is not None else None)
@@ -194,7 +209,7 @@ def lib() -> C.CDLL:
                 f"{LIB_PATH} is missing: build it with `python -c 'import __graft_entry__ as g; g.build()'` "
                 "(or `make -C mipsfusion_amd/csrc`). There is no CPU fallback.")
         handle = C.CDLL(LIB_PATH)
-        for name, (res, args) in SIGNATURES.items():
+        for name, (res, args) in list(SIGNATURES.items()) + list(MESH_SIGNATURES.items()):
             fn = getattr(handle, name)
             fn.restype = res
             fn.argtypes = args

@@ -1,5 +1,6 @@
 // Error state, ABI info and host-only helpers of libmipsf_hip.so.
 #include "common.h"
+#include "../../include/mipsf_mesh.h"
 
 #include <math.h>
 #include <string.h>
@@ -60,6 +61,15 @@ uint64_t mipsf_buffer_size(int which, uint32_t n, uint32_t a, uint32_t b, const 
         case MIPSF_SIZE_RENDER_PARTIAL: return mipsf::render_partial_floats(n);
         case MIPSF_SIZE_PLACE_POSE_SCRATCH: return mipsf::place_pose_scratch_floats(a, b, n);
         case MIPSF_SIZE_POSE_RAYS_SCRATCH: return mipsf::pose_rays_scratch_floats(a, b, n);
+        case MIPSF_SIZE_MCUBES_OFFSET_WORDS:
+        case MIPSF_SIZE_MCUBES_WELD_SLOTS:
+        case MIPSF_SIZE_MCUBES_WELD_WORDS: {
+            const uint64_t v = which == MIPSF_SIZE_MCUBES_OFFSET_WORDS ? mipsf::mcubes_offset_words(n, a, b)
+                             : which == MIPSF_SIZE_MCUBES_WELD_SLOTS   ? mipsf::mcubes_weld_slots(n)
+                                                                       : mipsf::mcubes_weld_words(n);
+            if (v == 0) { mipsf::set_error("mipsf_buffer_size: mesh buffer %d: volume or soup too large", which); return ~0ull; }
+            return v;
+        }
         default: mipsf::set_error("mipsf_buffer_size: unknown buffer %d", which); return ~0ull;
     }
 }

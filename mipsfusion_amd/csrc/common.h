@@ -40,6 +40,10 @@ uint64_t decoder_tile_words(uint32_t M);
 uint64_t render_partial_floats(uint32_t N);
 uint64_t place_pose_scratch_floats(uint32_t F, uint32_t K, uint32_t N);
 uint64_t pose_rays_scratch_floats(uint32_t F, uint32_t K, uint32_t N);
+// mesh extractor (mcubes.hip, include/mipsf_mesh.h); 0 = the volume / soup is too large
+uint64_t mcubes_offset_words(uint32_t X, uint32_t Y, uint32_t Z);
+uint64_t mcubes_weld_slots(uint32_t T);
+uint64_t mcubes_weld_words(uint32_t T);
 
 #define MIPSF_REQUIRE(cond, ...)                 \
     do {                                         \
