@@ -8,6 +8,7 @@ fallback: using an operator without the built library or without a GPU raises.
 __version__ = "0.1.0"
 
 _MESH = ("marching_cubes", "extract_mesh", "extract_mesh2", "Mesh", "save_ply", "load_ply")
+_SCENE_MESH = ("SubMap", "FusedVolume", "fuse_volume", "extract_scene_mesh", "submap_from_mesh", "voxel_occupancy", "point_mask")
 
 
 def __getattr__(name):
@@ -15,4 +16,7 @@ def __getattr__(name):
     if name in _MESH:
         from . import mesh
         return getattr(mesh, name)
+    if name in _SCENE_MESH:                 # the scene as one mesh (mipsfusion_amd/scene_mesh.py), the same way
+        from . import scene_mesh
+        return getattr(scene_mesh, name)
     raise AttributeError(f"module {__name__!r} has no attribute {name!r}")

@@ -189,6 +189,42 @@ MESH_SIGNATURES = {
 }
 
 
+# include/mipsf_fuse.h (the scene as one mesh: visibility, SDF fusion, connected components)
+FUSE_KF_FLOATS = 16
+FUSE_IN_BOX, FUSE_SEEN = 1, 2
+
+
+class FusePoints(C.Structure):
+    _fields_ = [("points", _VP), ("ticks", _VP * 3), ("dims", _CU * 3), ("lo", _CU * 3), ("size", _CU * 3), ("first", _CU), ("n", _CU)]
+
+
+class FuseCamera(C.Structure):
+    _fields_ = [("fx", C.c_float), ("fy", C.c_float), ("cx", C.c_float), ("cy", C.c_float), ("W", C.c_float), ("H", C.c_float),
+                ("edge", C.c_float), ("k", _CU), ("keyframes", _VP)]
+
+
+FuseVisibilityArgs = _args("FuseVisibilityArgs", [("pts", FusePoints), ("cam", FuseCamera), ("seen", _VP)])
+FuseLocalArgs = _args("FuseLocalArgs", [("pts", FusePoints), ("w2l", C.c_float * 12), ("sub", C.c_double * 3), ("div", C.c_double * 3),
+                                        ("out", _VP)])
+FuseAccumulateArgs = _args("FuseAccumulateArgs", [("pts", FusePoints), ("cam", FuseCamera), ("rows", _VP), ("n_rows", _CU),
+                                                  ("channels", _CU), ("sigmoid", _CU), ("values", _VP), ("entropy", _VP),
+                                                  ("value_stride", _CU), ("entropy_stride", _CU), ("use_obb", _CU),
+                                                  ("obb_centre", C.c_double * 3), ("obb_axes", C.c_double * 9),
+                                                  ("obb_half", C.c_double * 3), ("centroid", C.c_float * 3), ("sigma", C.c_float),
+                                                  ("gauss_k", C.c_float), ("num", _VP), ("den", _VP), ("flags", _VP)])
+FuseFinalizeArgs = _args("FuseFinalizeArgs", [("n", _CU), ("channels", _CU), ("num", _VP), ("den", _VP), ("flags", _VP), ("out", _VP),
+                                              ("volume", _VP)])
+FuseLabelArgs = _args("FuseLabelArgs", [("F", _CU), ("E", _CU), ("pairs", _VP), ("labels", _VP), ("counts", _VP), ("max_rounds", _CU),
+                                        ("resume", _CU)])
+FUSE_SIGNATURES = {
+    "mipsf_fuse_visibility": (_I, [C.POINTER(FuseVisibilityArgs), _P]),
+    "mipsf_fuse_local_points": (_I, [C.POINTER(FuseLocalArgs), _P]),
+    "mipsf_fuse_accumulate": (_I, [C.POINTER(FuseAccumulateArgs), _P]),
+    "mipsf_fuse_finalize": (_I, [C.POINTER(FuseFinalizeArgs), _P]),
+    "mipsf_fuse_label_components": (_I, [C.POINTER(FuseLabelArgs), _P]),
+}
+
+
 def buffer_size(which: int, n: int = 0, a: int = 0, b: int = 0, meta=None) -> int:
     """mipsf_buffer_size: elements of a scratch / record buffer (SIZE_* above)."""
     v = lib().mipsf_buffer_size(which, n, a, b, C.byref(meta) if meta is not None else None)
@@ -209,7 +245,7 @@ def lib() -> C.CDLL:
                 f"{LIB_PATH} is missing: build it with `python -c 'import __graft_entry__ as g; g.build()'` "
                 "(or `make -C mipsfusion_amd/csrc`). There is no CPU fallback.")
         handle = C.CDLL(LIB_PATH)
-        for name, (res, args) in list(SIGNATURES.items()) + list(MESH_SIGNATURES.items()):
+        for name, (res, args) in list(SIGNATURES.items()) + list(MESH_SIGNATURES.items()) + list(FUSE_SIGNATURES.items()):
             fn = getattr(handle, name)
             fn.restype = res
             fn.argtypes = args
