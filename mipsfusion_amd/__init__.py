@@ -9,6 +9,7 @@ __version__ = "0.1.0"
 
 _MESH = ("marching_cubes", "extract_mesh", "extract_mesh2", "Mesh", "save_ply", "load_ply")
 _SCENE_MESH = ("SubMap", "FusedVolume", "fuse_volume", "extract_scene_mesh", "submap_from_mesh", "voxel_occupancy", "point_mask")
+_POSE_CORRECTOR = ("cloud_from_rays", "estimate_normals", "registration_icp", "switch_pose_rectifying", "IcpResult")
 
 
 def __getattr__(name):
@@ -19,4 +20,7 @@ def __getattr__(name):
     if name in _SCENE_MESH:                 # the scene as one mesh (mipsfusion_amd/scene_mesh.py), the same way
         from . import scene_mesh
         return getattr(scene_mesh, name)
+    if name in _POSE_CORRECTOR:             # rectifying a switch pose by ICP (mipsfusion_amd/pose_corrector.py), the same way
+        from . import pose_corrector
+        return getattr(pose_corrector, name)
     raise AttributeError(f"module {__name__!r} has no attribute {name!r}")

@@ -225,6 +225,32 @@ FUSE_SIGNATURES = {
 }
 
 
+# include/mipsf_icp.h (rectifying a switch pose: clouds from ray rows, grid, nearest neighbours, normals, point-to-plane ICP)
+ICP_KNN = 30
+ICP_RESULT_DOUBLES = 20
+ICP_MAX_POINTS, ICP_MAX_CELLS = 1 << 27, 1 << 26
+ICP_WS_CLOUD, ICP_WS_GRID, ICP_WS_REGISTER = 1, 2, 3
+IcpCloudArgs = _args("IcpCloudArgs", [("n", _CU), ("k", _CU), ("rows_per_owner", _CU), ("rows", _VP), ("owner", _VP), ("poses", _VP),
+                                      ("points", _VP), ("count", _VP), ("workspace", _VP)])
+IcpBinArgs = _args("IcpBinArgs", [("n", _CU), ("max_cells", _CU), ("points", _VP), ("min_edge", C.c_double), ("grid", _VP)])
+IcpNearestArgs = _args("IcpNearestArgs", [("n_source", _CU), ("n_target", _CU), ("max_cells", _CU), ("source", _VP), ("grid", _VP),
+                                          ("max_dist", C.c_double), ("partner", _VP), ("d2", _VP)])
+IcpNormalsArgs = _args("IcpNormalsArgs", [("n", _CU), ("max_cells", _CU), ("points", _VP), ("grid", _VP), ("normals", _VP),
+                                          ("neighbours", _VP)])
+IcpRegisterArgs = _args("IcpRegisterArgs", [("n_source", _CU), ("n_target", _CU), ("max_cells", _CU), ("max_iteration", _CU),
+                                            ("source", _VP), ("grid", _VP), ("target_normals", _VP), ("max_dist", C.c_double),
+                                            ("relative_fitness", C.c_double), ("relative_rmse", C.c_double), ("result", _VP),
+                                            ("partner", _VP), ("workspace", _VP)])
+ICP_SIGNATURES = {
+    "mipsf_icp_workspace_bytes": (_U64, [_I, _U32, _U32]),
+    "mipsf_icp_cloud": (_I, [C.POINTER(IcpCloudArgs), _P]),
+    "mipsf_icp_bin": (_I, [C.POINTER(IcpBinArgs), _P]),
+    "mipsf_icp_nearest": (_I, [C.POINTER(IcpNearestArgs), _P]),
+    "mipsf_icp_normals": (_I, [C.POINTER(IcpNormalsArgs), _P]),
+    "mipsf_icp_register": (_I, [C.POINTER(IcpRegisterArgs), _P]),
+}
+
+
 def buffer_size(which: int, n: int = 0, a: int = 0, b: int = 0, meta=None) -> int:
     """mipsf_buffer_size: elements of a scratch / record buffer (SIZE_* above)."""
     v = lib().mipsf_buffer_size(which, n, a, b, C.byref(meta) if meta is not None else None)
@@ -245,7 +271,8 @@ def lib() -> C.CDLL:
                 f"{LIB_PATH} is missing: build it with `python -c 'import __graft_entry__ as g; g.build()'` "
                 "(or `make -C mipsfusion_amd/csrc`). There is no CPU fallback.")
         handle = C.CDLL(LIB_PATH)
-        for name, (res, args) in list(SIGNATURES.items()) + list(MESH_SIGNATURES.items()) + list(FUSE_SIGNATURES.items()):
+        for name, (res, args) in list(SIGNATURES.items()) + (list(MESH_SIGNATURES.items())
+                                       + list(FUSE_SIGNATURES.items()) + list(ICP_SIGNATURES.items())):
             fn = getattr(handle, name)
             fn.restype = res
             fn.argtypes = args

@@ -437,13 +437,20 @@ class GraphedSequence:
     What replaces host control plane here (out of scope): the switch decisions of Manager.py are the fixed
     ``schedule``; the sub-maps share one estimated world frame (the reference re-bases the pose to the new sub-map's first
     keyframe, mipsfusion.py:652 -- a rigid change of coordinates that moves no work; the miniature parity run of
-    tests/seq_harness.py keeps the reference's local frames), PoseCorrector's ICP rectification is dropped."""
+    tests/seq_harness.py keeps the reference's local frames).
+    ``rectify_switch=True`` (opt-in; off: nothing of it is reached) puts PoseCorrector.switch_pose_rectifying in front of the
+    refinement of a ("back", s) switch: the frame's down-sampled points are registered against the points of at most 10 of
+    s's keyframes by point-to-plane ICP on the device (mipsfusion_amd.pose_corrector, csrc/icp.hip), the
+    accepted result replaces the pose the refinement starts from, and ``rectified`` records (flag, n_correspondences) per
+    switch.  ``tracking.switch``'s align_threshold / including_last / min_correspondence / min_trans_dist are read with the
+    reference's shipped values as defaults (0.05, 0, 2000, 0.5).  The registration restates open3d's published algorithm;
+    upstream pins no open3d version, so nothing pins this step to a recorded upstream result."""
 
     INIT_INNER = 25          # iterations per replay of the sub-map initialisation graph (500 = 20 replays)
 
     def __init__(self, cfg, dev, frames, kf_every=15, sampler="reference", first_iters=None, stream=None,
                  lookahead=None, graph_ro=True, gate_producer=True, ro_precision=None, schedule=None, decoder_precision=None,
-                 device_handover=None, deterministic=None):
+                 device_handover=None, deterministic=None, rectify_switch=False):
         """lookahead: how many frames the sample producer runs ahead of the GPU (default: ``map_every``, one whole
         mapping period -- a BA round needs ~40 ms of serial generator work, a frame without BA ~4 ms, so the work only
         evens out over a period; the reference's own DataLoader prefetches 8 frames, mipsfusion.py:672).
@@ -453,7 +460,8 @@ class GraphedSequence:
         fp32 arithmetic; "f16x3" = the fast mode).  ro_precision: arithmetic of the RandomOptimizer rounds (default: the
         model's; "f16" = the opt-in plain-f16 rounds of BASELINE config 5, pose within 1e-3 of the reference's).
         deterministic: JointEncoding.deterministic of the model (default None: follow torch.are_deterministic_algorithms_enabled()
-        at capture time); True = fixed-order mapping backward, the same run gives the same trajectory bit for bit."""
+        at capture time); True = fixed-order mapping backward, the same run gives the same trajectory bit for bit.
+        rectify_switch: rectify the pose of every ("back", s) switch by ICP before its refinement (see the class docstring)."""
         from .RandomOptimizer import RandomOptimizer
         from .graph import GraphedSteps, work_stream
         from .model import JointEncoding
@@ -462,6 +470,8 @@ class GraphedSequence:
         assert sampler in ("reference", "device")
         self.cfg, self.dev, self.frames, self.sampler, self.kf_every = cfg, dev, frames, sampler, kf_every
         self.graph_ro = graph_ro and cfg["tracking"]["iter_RO"] > 0
+        self.rectify_switch = bool(rectify_switch)
+        self.rectified = []                                 # (flag, n_correspondences) of every rectified switch, in order
         # device_handover (default; MIPSF_SEQ_HOST_HANDOVER=1 or False = round 4's loop): a frame's three stages hand their
         # pose over ON THE DEVICE -- RandomOptimizer state -> tracking Parameters (ops.pose_handover), tracking Parameters ->
         # the BA round's current-frame slot (a 28-byte copy) -- and the host reads ONE pose back per frame, behind the last
@@ -911,7 +921,7 @@ class GraphedSequence:
     def _switch_back(self, target, pose, waiting):
         """active_submap_switch + local_BA_switch (mipsfusion.py:608-634, 379-444) -> the refined pose of the frame (CPU)"""
         self._store_active()
-        sm = self.submaps[target]
+        sm, previous = self.submaps[target], self.active
         with torch.no_grad():
             for dst, src in zip(self._state_tensors(), sm["state"]):
                 dst.copy_(src)                              # load_state_dict of the asked sub-map, device to device
@@ -924,6 +934,8 @@ class GraphedSequence:
             self.fixed[0].copy_(poses[0])
             if k > 1:
                 self.ba_rot.data[:k - 1].copy_(qt[1:, :4]), self.ba_trans.data[:k - 1].copy_(qt[1:, 4:])
+        if self.rectify_switch:
+            pose = waiting(lambda: self._rectify(slots, poses, previous, pose))
         self._set_pose(self.sw_rot, self.sw_trans, 0, pose)
         self.sw_popt.reset()
         n = self._fill_sw_device(slots)
@@ -931,6 +943,29 @@ class GraphedSequence:
         pose = waiting(lambda: self._get_pose(self.sw_rot, self.sw_trans, 0))
         self._add_keyframe(pose)                            # the overlapping keyframe joins the sub-map switched to
         return pose
+
+    def _rectify(self, slots, poses, previous, pose):
+        """PoseCorrector.switch_pose_rectifying in front of the switch refinement -> the pose it starts from (CPU).  The sub-maps
+        share one world frame here, so the keyframe poses and the frame's pose enter as they are; the keyframes are the (at
+        most 10) whose camera centres are nearest to the mean of the frame's points, Manager.py:296-307."""
+        from . import pose_corrector as pc
+        st = pc.switch_settings(self.cfg)
+        with torch.no_grad():
+            frame_rows = self.cur.view(self.H, self.W, 7)[self.kf_rows, self.kf_cols].contiguous()
+            pose32 = pose.detach().to(torch.float32).cpu()
+            chosen = list(range(len(slots)))
+            if len(chosen) > 10:
+                pts, _ = pc.cloud_from_rays(frame_rows, self.R, pose32.to(self.dev)[None].contiguous())
+                chosen = sorted(pc.nearest_keyframes(pts, poses[:, :3, 3], 10))
+            extra = None
+            if st["including_last"] > 0:
+                last = self.submaps[previous]["kfs"][-st["including_last"]:]
+                qt = self.kf_qt[self._slots_dev(last)]
+                extra = (self.db.rays[self._slots_dev(last)].reshape(-1, 7), self.R, qt_to_transform_matrix(qt[:, :4], qt[:, 4:]))
+            flag, n, out = pc.switch_pose_rectifying(self.db, [slots[i] for i in chosen], poses[chosen], frame_rows, pose32,
+                                                     self.cfg, extra_source=extra)
+        self.rectified.append((bool(flag), int(n)))
+        return out.to(pose.dtype) if flag else pose
 
     def _n_kf_at(self, k):
         """related keyframes when frame k's local BA runs (the frame itself is added AFTER its BA, mipsfusion.py:681-688)"""
@@ -1218,6 +1253,7 @@ class GraphedSequence:
             self.producer.close()
         return {"frame_ms": t_frame, "ro_ms": t_ro, "go_ms": t_go, "ba_ms": t_ba, "producer_wait_ms": t_wait,
                 "est": est, "capture_ms": self.capture_ms, "detail_ms": detail, "switch": t_switch,
+                "rectified": list(self.rectified),
                 "submaps": {s: list(v["kfs"]) for s, v in self.submaps.items()},
                 "producer_host_ms": dict(self.producer.host_ms) if self.producer is not None else None}
 
