@@ -77,6 +77,7 @@ typedef struct mipsf_grid_meta {
 #define MIPSF_SIZE_PLACE_POSE_SCRATCH 10      /* n = N, a = F, b = K: mipsf_place_pose_bwd                                  */
 #define MIPSF_SIZE_POSE_RAYS_SCRATCH 11       /* n = N, a = F, b = K: mipsf_pose_rays_bwd                                   */
 #define MIPSF_SIZE_HASHGRID_DET_SCRATCH 12    /* n = M, a = (dx != NULL), meta: mipsf_hashgrid_bwd with MIPSF_HG_DETERMINISTIC */
+#define MIPSF_SIZE_DECODER_LIVE_LIST 13       /* n = M: uint32 words of the live-sample list of mipsf_decoder_live_compact    */
 uint64_t mipsf_buffer_size(int which, uint32_t n, uint32_t a, uint32_t b, const mipsf_grid_meta* meta_host);
 
 /* --------------------------------------------------------------- hash grid (a5) */
@@ -274,6 +275,12 @@ int mipsf_decoder_fwd16(const mipsf_decoder_fwd16_args* args_host, void* stream)
 #define MIPSF_CHAIN_HEADER_CLEAR 1
 #define MIPSF_CHAIN_LEAN_DACT 2
 #define MIPSF_CHAIN_BF16X6 4
+/*   live_list  nullable: COMPACT MODE.  The list mipsf_decoder_live_compact of mipsf_compact.h made from THIS `dout` (which also wrote the zeros of
+ *              the dead samples into dfeat and dx).  Lane j of compact tile c works on sample live_list[MIPSF_LIVE_HEADER + 32 c
+ *              + j]: x, out, dout, the ReLU masks, dfeat, dx and the small rows of `dact` are addressed by that sample, the
+ *              large part of `dact` by the compact tile.  dfeat and dx of the listed samples are bit-identical to the call
+ *              without a list.  tile_live is then required: its header deals the compact tiles (its lists stay empty).
+ *              Hand both buffers to mipsf_decoder_wgrad16, and live_list to mipsf_hashgrid_dx_from_jac_list of mipsf_compact.h. */
 typedef struct mipsf_decoder_chain16_args {
     uint32_t struct_size;
     uint32_t M;
@@ -289,6 +296,7 @@ typedef struct mipsf_decoder_chain16_args {
     int feat_layout;
     int flags;
     uint32_t packed16_floats;       /* 0 = unchecked (see mipsf_decoder_fwd16_args) */
+    const uint32_t* live_list;      /* nullable: compact mode */
 } mipsf_decoder_chain16_args;
 int mipsf_decoder_bwd_chain16(const mipsf_decoder_chain16_args* args_host, void* stream);
 /* Weight gradients from the records by the STREAMING kernel of csrc/wgrad16.hip: the 16-bit matrix cores transpose the
@@ -303,7 +311,13 @@ int mipsf_decoder_bwd_chain16(const mipsf_decoder_chain16_args* args_host, void*
  *               (deterministic training).  Each of the eight lists in `tile_live` (if given) is first put in ascending tile
  *               order IN PLACE (members and counts unchanged): the chain appends tiles in the order they finish and this
  *               kernel deals list positions to its workgroups.  The per-workgroup records are then summed in block order by
- *               one thread per gradient element (the default reduce meets in float atomics).  M <= MIPSF_TILE_ORDER_MAX_M */
+ *               one thread per gradient element (the default reduce meets in float atomics).  M <= MIPSF_TILE_ORDER_MAX_M
+ *   live_list   nullable: COMPACT MODE behind mipsf_decoder_bwd_chain16 with the same list: `dact` is read by compact tile, the
+ *               forward's record, the masks, x, the grid features and the small rows by the listed sample.  Only the
+ *               transpose-read exchange form takes it (F16X3 / BF16X6 with packed16), with `saved` below 4 GiB; tile_live is
+ *               ignored.  The gradients differ from the call without a list by the grouping of their fp32 sums only.  With
+ *               MIPSF_WGRAD_DETERMINISTIC nothing needs ordering: the list is ascending whatever the schedule and its tiles
+ *               are visited in a fixed order; the ordered reduce follows as above. */
 #define MIPSF_WGRAD_LEAN_DACT 1u
 #define MIPSF_WGRAD_DETERMINISTIC 2u
 #define MIPSF_TILE_ORDER_MAX_M (1u << 27)
@@ -322,6 +336,7 @@ typedef struct mipsf_decoder_wgrad16_args {
     int arithmetic;
     uint32_t flags;
     uint32_t packed16_floats;       /* 0 = unchecked (see mipsf_decoder_fwd16_args) */
+    const uint32_t* live_list;      /* nullable: compact mode */
 } mipsf_decoder_wgrad16_args;
 int mipsf_decoder_wgrad16(const mipsf_decoder_wgrad16_args* args_host, void* stream);
 

@@ -65,11 +65,12 @@ DecoderFwd16Args = _args("DecoderFwd16Args", [("M", _CU), ("packed16", _VP), ("f
                                               ("sdf_only", _CI), ("lean_record", _CI), ("packed16_floats", _CU)])
 DecoderChain16Args = _args("DecoderChain16Args", [("M", _CU), ("packed16", _VP), ("x", _VP), ("out", _VP), ("dout", _VP),
                                                   ("saved", _VP), ("dfeat", _VP), ("dx", _VP), ("dact", _VP), ("tile_live", _VP),
-                                                  ("feat_layout", _CI), ("flags", _CI), ("packed16_floats", _CU)])
+                                                  ("feat_layout", _CI), ("flags", _CI), ("packed16_floats", _CU),
+                                                  ("live_list", _VP)])
 DecoderWgrad16Args = _args("DecoderWgrad16Args", [("M", _CU), ("packed16", _VP), ("feat", _VP), ("x", _VP), ("saved", _VP),
                                                   ("dact", _VP), ("tile_live", _VP), ("grads", C.POINTER(DecoderGrads)),
                                                   ("partial", _VP), ("feat_layout", _CI), ("arithmetic", _CI), ("flags", _CU),
-                                                  ("packed16_floats", _CU)])
+                                                  ("packed16_floats", _CU), ("live_list", _VP)])
 RenderFwdArgs = _args("RenderFwdArgs", [("N", _CU), ("S", _CU), ("raw", _VP), ("z_vals", _VP), ("target_rgb", _VP), ("target_d", _VP),
                                         ("counts", _VP), ("cfg", C.POINTER(RenderCfg)), ("rgb", _VP), ("depth", _VP),
                                         ("depth_var", _VP), ("disp", _VP), ("acc", _VP), ("weights", _VP), ("losses", _VP),
@@ -84,7 +85,9 @@ RENDER_BWD_KEEP_IF_UNIT = 1
 # mipsf_buffer_size(which, n, a, b, meta): MIPSF_SIZE_* of include/mipsf.h
 (SIZE_HASHGRID_BWD_SCRATCH, SIZE_HASHGRID_COUNTER_WORDS, SIZE_DECODER_PACKED, SIZE_DECODER_SAVED, SIZE_DECODER_DACT,
  SIZE_DECODER_WGRAD_PARTIAL, SIZE_DECODER_PACKED16, SIZE_DECODER_TILE_WORDS, SIZE_RENDER_PARTIAL, SIZE_PLACE_POSE_SCRATCH,
- SIZE_POSE_RAYS_SCRATCH, SIZE_HASHGRID_DET_SCRATCH) = range(1, 13)
+ SIZE_POSE_RAYS_SCRATCH, SIZE_HASHGRID_DET_SCRATCH, SIZE_DECODER_LIVE_LIST) = range(1, 14)
+# live-sample list of mipsf_decoder_live_compact (MIPSF_LIVE_*)
+LIVE_HEADER, LIVE_PAD = 16, 0xFFFFFFFF
 
 # mipsf_hashgrid_bwd flags (MIPSF_HG_*) and the deterministic scatter's constants
 HG_DPARAMS_ZERO, HG_ROUTED, HG_DETERMINISTIC = 1, 2, 4
@@ -182,6 +185,12 @@ McubesArgs = _args("McubesArgs", [("X", _CU), ("Y", _CU), ("Z", _CU), ("isovalue
                                   ("capacity_tris", _CU)])
 McubesWeldArgs = _args("McubesWeldArgs", [("T", _CU), ("soup", _VP), ("scratch", _VP), ("vertices", _VP), ("faces", _VP),
                                           ("counts", _VP), ("max_rounds", _CU)])
+# include/mipsf_compact.h
+COMPACT_SIGNATURES = {
+    "mipsf_decoder_live_compact": (_I, [_P, _U32, _P, _P, _P, _I, _P]),
+    "mipsf_hashgrid_dx_from_jac_list": (_I, [_P, _P, _P, _P, _U32, C.POINTER(GridMeta), _I, _P]),
+}
+
 MESH_SIGNATURES = {
     "mipsf_mcubes_count": (_I, [C.POINTER(McubesArgs), _P]),
     "mipsf_mcubes_emit": (_I, [C.POINTER(McubesArgs), _P]),
@@ -272,7 +281,8 @@ def lib() -> C.CDLL:
                 "(or `make -C mipsfusion_amd/csrc`). There is no CPU fallback.")
         handle = C.CDLL(LIB_PATH)
         for name, (res, args) in list(SIGNATURES.items()) + (list(MESH_SIGNATURES.items())
-                                       + list(FUSE_SIGNATURES.items()) + list(ICP_SIGNATURES.items())):
+                                       + list(FUSE_SIGNATURES.items()) + list(ICP_SIGNATURES.items())
+                                       + list(COMPACT_SIGNATURES.items())):
             fn = getattr(handle, name)
             fn.restype = res
             fn.argtypes = args

@@ -58,6 +58,7 @@ uint64_t mipsf_buffer_size(int which, uint32_t n, uint32_t a, uint32_t b, const 
         case MIPSF_SIZE_DECODER_WGRAD_PARTIAL: return mipsf::decoder_wgrad_partial_floats();
         case MIPSF_SIZE_DECODER_PACKED16: return mipsf::decoder_packed16_floats((int)a);
         case MIPSF_SIZE_DECODER_TILE_WORDS: return mipsf::decoder_tile_words(n);
+        case MIPSF_SIZE_DECODER_LIVE_LIST: return mipsf::decoder_live_list_words(n);
         case MIPSF_SIZE_RENDER_PARTIAL: return mipsf::render_partial_floats(n);
         case MIPSF_SIZE_PLACE_POSE_SCRATCH: return mipsf::place_pose_scratch_floats(a, b, n);
         case MIPSF_SIZE_POSE_RAYS_SCRATCH: return mipsf::pose_rays_scratch_floats(a, b, n);

@@ -6,6 +6,7 @@
 #include <stdio.h>
 
 #include "../../include/mipsf.h"
+#include "../../include/mipsf_compact.h"
 
 #define MIPSF_WAVE 64
 
@@ -37,6 +38,7 @@ uint64_t decoder_dact_floats(uint32_t M);
 uint64_t decoder_wgrad_partial_floats();
 uint64_t decoder_packed16_floats(int precision);
 uint64_t decoder_tile_words(uint32_t M);
+uint64_t decoder_live_list_words(uint32_t M);
 uint64_t render_partial_floats(uint32_t N);
 uint64_t place_pose_scratch_floats(uint32_t F, uint32_t K, uint32_t N);
 uint64_t pose_rays_scratch_floats(uint32_t F, uint32_t K, uint32_t N);

@@ -842,18 +842,114 @@ __global__ __launch_bounds__(TL_ORDER_BLOCK) void tile_lists_order_kernel(uint32
     }
 }
 
-template <int LAYOUT, int NP, typename Img>
+// LIVE-SAMPLE LIST (mipsf_decoder_live_compact; layout in include/mipsf.h).  A tile of the chain is 32 samples of one ray and
+// the live samples of a ray are a prefix of it: on the mapping workload 0.65 of the tiles are live but only 0.48 of the
+// samples, so a quarter of the columns of every product of the chain and of the weight-gradient kernel belong to samples whose
+// contribution is exactly zero.  A sample is one column of the B operand and everything about it is addressed per lane, so any
+// 32 live samples make a tile: the list packs them, in ascending order, and the two kernels work through compact tiles.
+// Behind the list entries the buffer holds [one count per LC_BLOCK samples, padded to an even number][one bit per sample].
+//   launch 1 (live_flag_kernel): the flags as wave ballots, the count of every block, zeros into dfeat / dx of the dead samples
+//   launch 2 (live_list_kernel): block b starts at the sum of the counts before it; a sample's position is that plus the set
+//                                bits before its own.  The last block writes the header and the pad entries.
+constexpr uint32_t LC_BLOCK = 1024;
+__host__ __device__ inline uint32_t lc_blocks(uint32_t M) { return (uint32_t)(((uint64_t)M + LC_BLOCK - 1) / LC_BLOCK); }
+__host__ __device__ inline uint64_t lc_counts_at(uint32_t M) { return MIPSF_LIVE_HEADER + 32ull * (((uint64_t)M + 31) / 32); }
+__host__ __device__ inline uint64_t lc_bits_at(uint32_t M) { return lc_counts_at(M) + ((lc_blocks(M) + 1u) & ~1u); }
+
+template <int LAYOUT>
+__global__ __launch_bounds__(LC_BLOCK) void live_flag_kernel(const float* __restrict__ dout, uint32_t M, uint32_t* __restrict__ ll,
+                                                             float* __restrict__ dfeat, float* __restrict__ dx) {
+    __shared__ uint32_t wcount[LC_BLOCK / MIPSF_WAVE];
+    const uint32_t t = threadIdx.x, w = t / MIPSF_WAVE, lane = t % MIPSF_WAVE;
+    const uint64_t s = (uint64_t)blockIdx.x * LC_BLOCK + t;
+    bool live = false;
+    if (s < M) {
+        const float2* g = reinterpret_cast<const float2*>(dout + s * 10);
+#pragma unroll
+        for (int c = 0; c < 5; ++c) {
+            const float2 v = g[c];
+            live = live || !(v.x == 0.0f && v.y == 0.0f);
+        }
+        if (!live) {
+            if (LAYOUT == MIPSF_FEAT_AOS) {
+                float4* d = reinterpret_cast<float4*>(dfeat + s * N_GRID);
+#pragma unroll
+                for (int q = 0; q < N_GRID / 4; ++q) d[q] = make_float4(0.f, 0.f, 0.f, 0.f);
+            } else {
+#pragma unroll
+                for (int l = 0; l < N_GRID / 2; ++l) *reinterpret_cast<float2*>(dfeat + ((size_t)l * M + s) * 2) = make_float2(0.f, 0.f);
+            }
+            dx[3 * s] = 0.f, dx[3 * s + 1] = 0.f, dx[3 * s + 2] = 0.f;
+        }
+    }
+    const uint64_t b = __ballot(live);
+    if (lane == 0) {
+        wcount[w] = (uint32_t)__popcll(b);
+        if ((uint64_t)blockIdx.x * LC_BLOCK + (uint64_t)w * MIPSF_WAVE < M) {       // (the bit words cover ceil(M / 32) * 32 samples)
+            uint32_t* bits = ll + lc_bits_at(M) + ((uint64_t)blockIdx.x * LC_BLOCK + (uint64_t)w * MIPSF_WAVE) / 32;
+            bits[0] = (uint32_t)b;
+            if ((uint64_t)blockIdx.x * LC_BLOCK + (uint64_t)w * MIPSF_WAVE + 32 < M) bits[1] = (uint32_t)(b >> 32);
+        }
+    }
+    __syncthreads();
+    if (t == 0) {
+        uint32_t n = 0;
+        for (uint32_t v = 0; v < LC_BLOCK / MIPSF_WAVE; ++v) n += wcount[v];
+        ll[lc_counts_at(M) + blockIdx.x] = n;
+    }
+}
+
+__global__ __launch_bounds__(LC_BLOCK) void live_list_kernel(uint32_t M, uint32_t* __restrict__ ll) {
+    __shared__ uint32_t wsum[LC_BLOCK / MIPSF_WAVE];
+    __shared__ uint32_t wbits[LC_BLOCK / 32];
+    const uint32_t t = threadIdx.x, w = t / MIPSF_WAVE, lane = t % MIPSF_WAVE;
+    const uint32_t* counts = ll + lc_counts_at(M);
+    const uint32_t* bits = ll + lc_bits_at(M);
+    // the samples before this block
+    uint32_t part = 0;
+    for (uint32_t k = t; k < blockIdx.x; k += LC_BLOCK) part += counts[k];
+#pragma unroll
+    for (int o = 1; o < MIPSF_WAVE; o <<= 1) part += __shfl_xor(part, o, MIPSF_WAVE);
+    if (lane == 0) wsum[w] = part;
+    if (t < LC_BLOCK / 32) {
+        const uint64_t first = (uint64_t)blockIdx.x * LC_BLOCK + 32ull * t;
+        wbits[t] = first < M ? bits[first / 32] : 0u;
+    }
+    __syncthreads();
+    uint32_t pos = 0;
+    for (uint32_t v = 0; v < LC_BLOCK / MIPSF_WAVE; ++v) pos += wsum[v];
+    for (uint32_t v = 0; v < 2 * w; ++v) pos += (uint32_t)__popc(wbits[v]);
+    const uint32_t lo = wbits[2 * w], hi = wbits[2 * w + 1];
+    const uint64_t s = (uint64_t)blockIdx.x * LC_BLOCK + t;
+    const bool live = ((lane < 32 ? lo >> lane : hi >> (lane - 32)) & 1u) != 0u && s < M;
+    pos += lane < 32 ? (uint32_t)__popc(lo & ((1u << lane) - 1u)) : (uint32_t)__popc(lo) + (uint32_t)__popc(hi & ((1u << (lane - 32)) - 1u));
+    if (live) ll[MIPSF_LIVE_HEADER + pos] = (uint32_t)s;
+    if (blockIdx.x == gridDim.x - 1) {
+        uint32_t total = 0;
+        for (uint32_t v = 0; v < LC_BLOCK / MIPSF_WAVE; ++v) total += wsum[v];
+        for (uint32_t v = 0; v < LC_BLOCK / 32; ++v) total += (uint32_t)__popc(wbits[v]);
+        const uint32_t padded = (total + 31u) & ~31u;              // <= 32 ceil(M / 32): inside the list
+        if (t < padded - total) ll[MIPSF_LIVE_HEADER + total + t] = MIPSF_LIVE_PAD;
+        if (t == 0) ll[0] = total, ll[1] = padded / 32u;
+    }
+}
+
+// COMPACT: `tile` is a compact tile of the live-sample list `live_idx` (its entries, past the header): lane j works on sample
+// live_idx[32 tile + j] and addresses everything of that sample by it; only the gradient record `dact` sits at the compact tile.
+// A pad entry (>= M) behaves as a lane past the end of the batch: zeros into `dact`, no other store.
+template <int LAYOUT, int NP, bool COMPACT = false, typename Img>
 __device__ __forceinline__ void decoder16_bwd_tile(const Img bimg, const float* __restrict__ x,
                                                    const float* __restrict__ out, const float* __restrict__ dout,
                                                    const float* __restrict__ saved, float* __restrict__ dfeat,
                                                    float* __restrict__ dx, float* __restrict__ dact,
                                                    float* __restrict__ dsmall, uint32_t M, int64_t tile, int lane_in,
-                                                   uint32_t* __restrict__ tile_live = nullptr, bool lean_dact = false) {
+                                                   uint32_t* __restrict__ tile_live = nullptr, bool lean_dact = false,
+                                                   const uint32_t* __restrict__ live_idx = nullptr) {
     static_assert(NP == 2 || NP == 3, "the chain runs on split operands");
     int lane = lane_in;                        // opaque per tile: per-lane offsets are recomputed by every tile instead of being
     asm volatile("" : "+v"(lane));             // kept (and spilled) across the persistent kernel's tile loop (cf. the forward)
     const int j = lane & 31, h = lane >> 5;
-    const uint32_t s_raw = (uint32_t)(tile * 32 + j);
+    const uint32_t s_raw = COMPACT ? live_idx[tile * 32 + j] : (uint32_t)(tile * 32 + j);
     const bool live = s_raw < M;
     const uint32_t s = live ? s_raw : M - 1;
     const uint32_t lane16 = 16u * (uint32_t)lane;
@@ -883,7 +979,7 @@ __device__ __forceinline__ void decoder16_bwd_tile(const Img bimg, const float* 
     // 64 on the mapping workload), so a third of the 32-sample tiles are zero throughout (tools/micro/dout_zero_probe.py).
     // With `tile_live` the caller asks for them to be short-cut: d(features) and d(x) are written as zeros, nothing else is
     // read or written, and the tile is left out of the list of live tiles the weight-gradient kernel works from.
-    if (tile_live != nullptr) {
+    if (!COMPACT && tile_live != nullptr) {
         bool any = false;
 #pragma unroll
         for (int c = 0; c < 5; ++c) any = any || (live && !(g2[c].x == 0.0f && g2[c].y == 0.0f));
@@ -918,7 +1014,8 @@ __device__ __forceinline__ void decoder16_bwd_tile(const Img bimg, const float* 
     const float x0 = x[3 * (size_t)s], x1 = x[3 * (size_t)s + 1], x2 = x[3 * (size_t)s + 2];
 #endif
     const uint2* mk = reinterpret_cast<const uint2*>(saved + (((size_t)M + 127) / 128) * 4 * ACT_TILE_FLOATS) +
-                      (size_t)tile * (MASK_TILE_WORDS / 2) + lane;
+                      (COMPACT ? (size_t)(s >> 5) * (MASK_TILE_WORDS / 2) + ((s & 31u) + 32u * (uint32_t)h)
+                               : (size_t)tile * (MASK_TILE_WORDS / 2) + lane);
     const uint2 mk1 = mk[0], mk3 = mk[64];
     const uint32_t m1[2] = {mk1.x, mk1.y}, m3[2] = {mk3.x, mk3.y};
 
@@ -942,8 +1039,8 @@ __device__ __forceinline__ void decoder16_bwd_tile(const Img bimg, const float* 
         for (int c = 0; c < N_CLASS; ++c) dlg[c] = p[c] * (dp[c] - dot);
 #pragma unroll
         for (int c = 0; c < 3; ++c) drgb[c] = live ? gv[c] : 0.f;
-        if (h == 0 && dact != nullptr) {
-            float4* d4 = reinterpret_cast<float4*>(dsmall + (size_t)(tile * 32 + j) * 8);
+        if (h == 0 && dact != nullptr && (!COMPACT || live)) {
+            float4* d4 = reinterpret_cast<float4*>(dsmall + (COMPACT ? (size_t)s : (size_t)(tile * 32 + j)) * 8);
             d4[0] = make_float4(dlg[0], dlg[1], dlg[2], dlg[3]);
             d4[1] = make_float4(dlg[4], drgb[0], drgb[1], drgb[2]);
         }
@@ -1118,7 +1215,7 @@ __device__ __forceinline__ void decoder16_bwd_tile(const Img bimg, const float* 
 }
 
 // Small batches: four independent waves per workgroup, operand images from L2.
-template <int LAYOUT, int NP>
+template <int LAYOUT, int NP, bool COMPACT>
 __global__ __launch_bounds__(DEC_BLOCK, 2) void decoder16_bwd_kernel(const float* __restrict__ packed16,
                                                                      const float* __restrict__ x,
                                                                      const float* __restrict__ out,
@@ -1126,20 +1223,23 @@ __global__ __launch_bounds__(DEC_BLOCK, 2) void decoder16_bwd_kernel(const float
                                                                      const float* __restrict__ saved,
                                                                      float* __restrict__ dfeat, float* __restrict__ dx,
                                                                      float* __restrict__ dact, float* __restrict__ dsmall,
-                                                                     uint32_t M, uint32_t* __restrict__ tile_live, uint32_t lean_dact) {
+                                                                     uint32_t M, uint32_t* __restrict__ tile_live, uint32_t lean_dact,
+                                                                     const uint32_t* __restrict__ live_list) {
     const int lane = threadIdx.x & 63;
     const int64_t tile = (int64_t)blockIdx.x * (DEC_BLOCK / 64) + __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
     if (tile * 32 >= (int64_t)M) return;
+    if (COMPACT && tile >= (int64_t)live_list[1]) return;            // (the grid covers every tile of the batch)
     const ImgBuf bimg{make_srd(reinterpret_cast<const _Float16*>(packed16 + TAIL16_FLOATS) + OFF16_BWD_HALVES,
                                IMG16B_HALVES * 4), 0u, (uint32_t)IMG16B_HALVES * 2u, ext16_srd<NP>(packed16), (uint32_t)EXT16_BWD * 2u};
-    decoder16_bwd_tile<LAYOUT, NP>(bimg, x, out, dout, saved, dfeat, dx, dact, dsmall, M, tile, lane, tile_live, lean_dact != 0u);
+    decoder16_bwd_tile<LAYOUT, NP, COMPACT>(bimg, x, out, dout, saved, dfeat, dx, dact, dsmall, M, tile, lane, tile_live, lean_dact != 0u,
+                                            COMPACT ? live_list + MIPSF_LIVE_HEADER : nullptr);
 }
 
 // Large batches: persistent, one 8-wave workgroup per CU holding BOTH backward image sets in LDS: 2 x 80 KB = all 160 KB
 // of the CU (the backward needs no tables besides them).
 constexpr int B16_LDS_BYTES = IMG16B_HALVES * 4;
 static_assert(B16_LDS_BYTES <= 160 * 1024, "the backward image sets must fit the LDS of a CU");
-template <int LAYOUT, int NP>
+template <int LAYOUT, int NP, bool COMPACT>
 __global__ __launch_bounds__(F16_LDS_BLOCK, 1) void decoder16_bwd_lds_kernel(const float* __restrict__ packed16,
                                                                              const float* __restrict__ x,
                                                                              const float* __restrict__ out,
@@ -1149,8 +1249,12 @@ __global__ __launch_bounds__(F16_LDS_BLOCK, 1) void decoder16_bwd_lds_kernel(con
                                                                              float* __restrict__ dx,
                                                                              float* __restrict__ dact,
                                                                              float* __restrict__ dsmall, uint32_t M,
-                                                                             uint32_t n_tiles,
-                                                                             uint32_t* __restrict__ tile_live, uint32_t lean_dact) {
+                                                                             uint32_t n_tiles_all,
+                                                                             uint32_t* __restrict__ tile_live, uint32_t lean_dact,
+                                                                             const uint32_t* __restrict__ live_list) {
+    // COMPACT: the compact tiles of the live-sample list, their number read here (the launch does not depend on it)
+    const uint32_t n_tiles = COMPACT ? (uint32_t)__builtin_amdgcn_readfirstlane((int)live_list[1]) : n_tiles_all;
+    const uint32_t* live_idx = COMPACT ? live_list + MIPSF_LIVE_HEADER : nullptr;
     extern __shared__ __attribute__((aligned(16))) float4 wbuf[];
     lds_preload<F16_LDS_BLOCK>(wbuf, reinterpret_cast<const _Float16*>(packed16 + TAIL16_FLOATS) + OFF16_BWD_HALVES, B16_LDS_BYTES / 16);
     __syncthreads();
@@ -1177,9 +1281,9 @@ __global__ __launch_bounds__(F16_LDS_BLOCK, 1) void decoder16_bwd_lds_kernel(con
             uint32_t z = 0;
             asm volatile("" : "+v"(z));
             const h8* imgp = reinterpret_cast<const h8*>(wbuf + z);
-            decoder16_bwd_tile<LAYOUT, NP>(ImgLds{imgp, imgp + IMG16B_HALVES / 8, ext16_srd<NP>(packed16), (uint32_t)EXT16_BWD * 2u},
+            decoder16_bwd_tile<LAYOUT, NP, COMPACT>(ImgLds{imgp, imgp + IMG16B_HALVES / 8, ext16_srd<NP>(packed16), (uint32_t)EXT16_BWD * 2u},
                                        x, out, dout, saved, dfeat, dx, dact, dsmall,
-                                       M, (int64_t)tile, lane, tile_live, lean_dact != 0u);
+                                       M, (int64_t)tile, lane, tile_live, lean_dact != 0u, live_idx);
         }
         return;
     }
@@ -1190,9 +1294,9 @@ __global__ __launch_bounds__(F16_LDS_BLOCK, 1) void decoder16_bwd_lds_kernel(con
         uint32_t z = 0;
         asm volatile("" : "+v"(z));
         const h8* imgp = reinterpret_cast<const h8*>(wbuf + z);
-        decoder16_bwd_tile<LAYOUT, NP>(ImgLds{imgp, imgp + IMG16B_HALVES / 8, ext16_srd<NP>(packed16), (uint32_t)EXT16_BWD * 2u},
+        decoder16_bwd_tile<LAYOUT, NP, COMPACT>(ImgLds{imgp, imgp + IMG16B_HALVES / 8, ext16_srd<NP>(packed16), (uint32_t)EXT16_BWD * 2u},
                                    x, out, dout, saved, dfeat, dx, dact, dsmall, M,
-                                   (int64_t)tile, lane, tile_live, lean_dact != 0u);
+                                   (int64_t)tile, lane, tile_live, lean_dact != 0u, live_idx);
     }
 }
 
@@ -1261,6 +1365,7 @@ static uint32_t persist_min_tiles_per_cu() {
 }
 
 namespace mipsf {
+uint64_t decoder_live_list_words(uint32_t M) { return lc_bits_at(M) + ((uint64_t)M + 31) / 32; }
 uint64_t decoder_packed16_floats(int precision) {
     return precision == MIPSF_PREC_BF16X6 ? (uint64_t)PACKED16X_FLOATS : (uint64_t)PACKED16_FLOATS;
 }
@@ -1383,6 +1488,7 @@ int mipsf_decoder_bwd_chain16(const mipsf_decoder_chain16_args* a, void* stream)
     const float* packed16 = a->packed16; const int feat_layout = a->feat_layout; const float* x = a->x; const float* out = a->out;
     const float* dout = a->dout; const float* saved = a->saved; float* dfeat = a->dfeat; float* dx = a->dx; float* dact = a->dact;
     uint32_t* tile_live = a->tile_live; const int flags = a->flags; const uint32_t M = a->M;
+    const uint32_t* live_list = a->live_list;
     {
         const int fam = (flags & MIPSF_CHAIN_BF16X6) ? MIPSF_PREC_BF16X6 : MIPSF_PREC_F16X3;
         MIPSF_REQUIRE(a->packed16_floats == 0u || a->packed16_floats == decoder_packed16_floats(fam),
@@ -1396,6 +1502,7 @@ int mipsf_decoder_bwd_chain16(const mipsf_decoder_chain16_args* a, void* stream)
     const uint32_t lean_dact = (flags & MIPSF_CHAIN_LEAN_DACT) ? 1u : 0u;
     MIPSF_REQUIRE(packed16 && x && out && dout && saved && dfeat && dx, "null pointer");      // (dact may be NULL: see the header)
     MIPSF_REQUIRE(feat_layout == MIPSF_FEAT_AOS || feat_layout == MIPSF_FEAT_LEVEL_MAJOR, "bad layout");
+    MIPSF_REQUIRE(live_list == nullptr || tile_live != nullptr, "the chain over a live-sample list deals its tiles through tile_live's header");
     const uint64_t n_bt = ((uint64_t)M + 127) / 128;
     const uint32_t blocks = (uint32_t)((((uint64_t)M + 31) / 32 + 3) / 4);
     float* dsmall = dact ? dact + n_bt * 4 * ACT_TILE_FLOATS : nullptr;
@@ -1410,23 +1517,27 @@ int mipsf_decoder_bwd_chain16(const mipsf_decoder_chain16_args* a, void* stream)
     }
 #define B16(LAY, NPL)                                                                                              \
     do {                                                                                                           \
+        if (live_list) B16C(LAY, NPL, true); else B16C(LAY, NPL, false);                                           \
+    } while (0)
+#define B16C(LAY, NPL, CMP)                                                                                        \
+    do {                                                                                                           \
         if (persistent) {                                                                                          \
             static bool attr_set_dev[MAX_DEVICES] = {false};                                                       \
             bool& attr_set = attr_set_dev[device_slot()];                                                          \
             if (!attr_set) {                                                                                       \
-                if (hipFuncSetAttribute((const void*)decoder16_bwd_lds_kernel<LAY, NPL>,                           \
+                if (hipFuncSetAttribute((const void*)decoder16_bwd_lds_kernel<LAY, NPL, CMP>,                          \
                                         hipFuncAttributeMaxDynamicSharedMemorySize, B16_LDS_BYTES) != hipSuccess) { \
                     set_error("cannot raise dynamic LDS to %d bytes", B16_LDS_BYTES);                              \
                     return 4;                                                                                      \
                 }                                                                                                  \
                 attr_set = true;                                                                                   \
             }                                                                                                      \
-            hipLaunchKernelGGL((decoder16_bwd_lds_kernel<LAY, NPL>), dim3(cus), dim3(F16_LDS_BLOCK), B16_LDS_BYTES, s, \
+            hipLaunchKernelGGL((decoder16_bwd_lds_kernel<LAY, NPL, CMP>), dim3(cus), dim3(F16_LDS_BLOCK), B16_LDS_BYTES, s, \
                                packed16, x, out, dout, saved, dfeat, dx, dact, dsmall, M, n_tiles, tile_live,      \
-                               lean_dact);                                                                         \
+                               lean_dact, live_list);                                                              \
         } else {                                                                                                   \
-            hipLaunchKernelGGL((decoder16_bwd_kernel<LAY, NPL>), dim3(blocks), dim3(DEC_BLOCK), 0, s, packed16, x, out, \
-                               dout, saved, dfeat, dx, dact, dsmall, M, tile_live, lean_dact);                     \
+            hipLaunchKernelGGL((decoder16_bwd_kernel<LAY, NPL, CMP>), dim3(blocks), dim3(DEC_BLOCK), 0, s, packed16, x, out, \
+                               dout, saved, dfeat, dx, dact, dsmall, M, tile_live, lean_dact, live_list);          \
         }                                                                                                          \
     } while (0)
     if (feat_layout == MIPSF_FEAT_AOS) {
@@ -1435,7 +1546,30 @@ int mipsf_decoder_bwd_chain16(const mipsf_decoder_chain16_args* a, void* stream)
         if (bf) B16(MIPSF_FEAT_LEVEL_MAJOR, 3); else B16(MIPSF_FEAT_LEVEL_MAJOR, 2);
     }
 #undef B16
+#undef B16C
     return check_launch("decoder_bwd_chain16");
+}
+
+int mipsf_decoder_live_compact(const float* dout, uint32_t M, uint32_t* live_list, float* dfeat, float* dx, int feat_layout,
+                               void* stream) {
+    MIPSF_REQUIRE(live_list != nullptr, "null live_list");
+    MIPSF_REQUIRE(feat_layout == MIPSF_FEAT_AOS || feat_layout == MIPSF_FEAT_LEVEL_MAJOR, "bad layout");
+    hipStream_t s = (hipStream_t)stream;
+    if (M == 0) {
+        if (hipMemsetAsync(live_list, 0, 2 * sizeof(uint32_t), s) != hipSuccess) {
+            set_error("cannot clear the header of the live-sample list");
+            return 4;
+        }
+        return 0;
+    }
+    MIPSF_REQUIRE(dout && dfeat && dx, "null pointer");
+    const uint32_t blocks = lc_blocks(M);
+    if (feat_layout == MIPSF_FEAT_AOS)
+        hipLaunchKernelGGL(live_flag_kernel<MIPSF_FEAT_AOS>, dim3(blocks), dim3(LC_BLOCK), 0, s, dout, M, live_list, dfeat, dx);
+    else
+        hipLaunchKernelGGL(live_flag_kernel<MIPSF_FEAT_LEVEL_MAJOR>, dim3(blocks), dim3(LC_BLOCK), 0, s, dout, M, live_list, dfeat, dx);
+    hipLaunchKernelGGL(live_list_kernel, dim3(blocks), dim3(LC_BLOCK), 0, s, M, live_list);
+    return check_launch("decoder_live_compact");
 }
 
 }  // extern "C"

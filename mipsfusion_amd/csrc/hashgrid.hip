@@ -1172,12 +1172,18 @@ __global__ __launch_bounds__(256) void hashgrid_dx_reduce_kernel(const float* __
 // tiles (optional): the live-tile lists of the decoder's backward chain (decoder16.hip / decoder_layout.h).  Thread t then
 // works on sample 32 * tile(t / 32) + t % 32 of the listed tiles only: the others have a zero feature gradient, add
 // nothing, and their 384 bytes of Jacobian per sample stay unread.
+// live_list (optional, instead of tiles): the live-sample list of mipsf_decoder_live_compact; thread t works on its t-th entry.
 template <int LAYOUT>
 MIPSF_SINGLE_FP32 __global__ __launch_bounds__(256) void hashgrid_dx_jac_kernel(const float* __restrict__ jac,
                                                               const float* __restrict__ dout, float* __restrict__ dx,
                                                               uint32_t M, uint32_t L,
-                                                              const uint32_t* __restrict__ tiles) {
+                                                              const uint32_t* __restrict__ tiles,
+                                                              const uint32_t* __restrict__ live_list) {
     uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (live_list != nullptr) {
+        if (i >= M || i >= live_list[0]) return;
+        i = live_list[MIPSF_LIVE_HEADER + i];
+    }
     if (tiles != nullptr) {
         const uint32_t k = i >> 5, cap = mipsf::dl::tl_cap((M + 31u) / 32u);
         uint32_t q = 0, first = 0, total = 0;
@@ -1597,8 +1603,8 @@ int mipsf_hashgrid_fwd(const float* x, const float* params, float* out, float* j
     return hashgrid_fwd_impl(x, params, out, jac, M, meta, layout, stream);
 }
 
-int mipsf_hashgrid_dx_from_jac(const float* jac, const float* dout, float* dx, const uint32_t* tile_live, uint32_t M,
-                               const mipsf_grid_meta* meta, int layout, void* stream) {
+static int dx_from_jac(const float* jac, const float* dout, float* dx, const uint32_t* tile_live, const uint32_t* live_list, uint32_t M,
+                       const mipsf_grid_meta* meta, int layout, void* stream) {
     GridLevels g;
     if (int rc = to_levels(meta, g)) return rc;
     if (M == 0) return 0;
@@ -1606,10 +1612,19 @@ int mipsf_hashgrid_dx_from_jac(const float* jac, const float* dout, float* dx, c
     MIPSF_REQUIRE(layout == MIPSF_FEAT_AOS || layout == MIPSF_FEAT_LEVEL_MAJOR, "bad layout %d", layout);
     hipStream_t s = (hipStream_t)stream;
     if (layout == MIPSF_FEAT_AOS)
-        hipLaunchKernelGGL(hashgrid_dx_jac_kernel<MIPSF_FEAT_AOS>, dim3((M + 255) / 256), dim3(256), 0, s, jac, dout, dx, M, g.n_levels, tile_live);
+        hipLaunchKernelGGL(hashgrid_dx_jac_kernel<MIPSF_FEAT_AOS>, dim3((M + 255) / 256), dim3(256), 0, s, jac, dout, dx, M, g.n_levels, tile_live, live_list);
     else
-        hipLaunchKernelGGL(hashgrid_dx_jac_kernel<MIPSF_FEAT_LEVEL_MAJOR>, dim3((M + 255) / 256), dim3(256), 0, s, jac, dout, dx, M, g.n_levels, tile_live);
+        hipLaunchKernelGGL(hashgrid_dx_jac_kernel<MIPSF_FEAT_LEVEL_MAJOR>, dim3((M + 255) / 256), dim3(256), 0, s, jac, dout, dx, M, g.n_levels, tile_live, live_list);
     return check_launch("hashgrid_dx_from_jac");
+}
+int mipsf_hashgrid_dx_from_jac(const float* jac, const float* dout, float* dx, const uint32_t* tile_live, uint32_t M,
+                               const mipsf_grid_meta* meta, int layout, void* stream) {
+    return dx_from_jac(jac, dout, dx, tile_live, nullptr, M, meta, layout, stream);
+}
+int mipsf_hashgrid_dx_from_jac_list(const float* jac, const float* dout, float* dx, const uint32_t* live_list, uint32_t M,
+                                    const mipsf_grid_meta* meta, int layout, void* stream) {
+    MIPSF_REQUIRE(live_list != nullptr, "null live_list");
+    return dx_from_jac(jac, dout, dx, nullptr, live_list, M, meta, layout, stream);
 }
 
 }  // extern "C"

@@ -261,6 +261,10 @@ struct W16Args {
     // lean gradient record (MIPSF_WGRAD_LEAN_DACT, exchange form only): dG3 and the rgb_emb half of dH2 are recomputed
     const h8* gimg;                     // LDS: [S2T hi: 4 row tiles][S2T lo: 4][RGBT hi: 2][RGBT lo: 2] x 64 operands, or null
     const uint2* masks;                 // the ReLU mask part of `saved`
+    // compact mode (transpose-read exchange form only): the entries of the live-sample list (mipsf_decoder_live_compact) or null.
+    // `dact` is then read by compact tile; lane j of tile c reads everything else at sample lidx[32 c + j]
+    const uint32_t* lidx;
+    uint32_t saved_bytes;               // bytes of the record part of `saved`: one buffer resource spans it (below 4 GiB)
 };
 
 // the it-th tile of a pass, last first: the records the chain kernel wrote last are still in the 256 MB Infinity Cache
@@ -1562,7 +1566,10 @@ struct W16T {
 // waves 0..3 (w): d w_pts2[w][0..3] = dH2[w]^T H1, d b_pts2; d w_sdf2[:, 32 w ..] = (d logits)^T H3[w]; d w_rgb0 columns
 // {rgb_emb 0 | rgb_emb 1 | e 0 | e 1}[w] = (d rgb)^T ...; wave 3: the small rows' bias gradients.  Produces e k-step w and
 // H1 column tile w.
-template <int LAYOUT, typename A>
+// CP (both roles): compact mode, see W16Args::lidx.  A lane's sample is an entry of the list, loaded two tiles (role a: three)
+// ahead of the loads it addresses; a pad entry reads zeros for its small rows (past the end of their resource) and, like a lane
+// past the end of the batch, finite values of the last sample for the rest: its gradients in `dact` are zeros.
+template <int LAYOUT, typename A, bool CP>
 __device__ __forceinline__ void w16t_role_a(const W16Args& a, const W16T<A>& lx, int w, int lane) {
     typedef W16XL<A> L;
     typedef typename A::v8 v8;
@@ -1580,12 +1587,28 @@ __device__ __forceinline__ void w16t_role_a(const W16Args& a, const W16T<A>& lx,
 #pragma unroll
     for (int u = 0; u < 8; ++u) bacc[0][u] = 0.f, bacc[1][u] = 0.f;
     int k_main = 0, k_small = 0;
-    auto act_srd = [&](const float* recs, uint32_t tile) {
-        return make_srd(recs + (size_t)tile * ACT_TILE_FLOATS, ACT_TILE_FLOATS * 4);
-    };
     const srd_t small_srd = make_srd(a.dsmall, a.M * 32u), x_srd = make_srd(a.x, a.M * 12u);
-    auto load_small = [&](uint32_t tile, f32x8 (&v)[2]) {
-        const uint32_t off = (tile * 32u + (uint32_t)j) * 32u;
+    const uint32_t g = gridDim.x;
+    // lane j's sample of tile `tile`
+    auto samp = [&](uint32_t tile) -> uint32_t { return CP ? a.lidx[tile * 32u + (uint32_t)j] : tile * 32u + (uint32_t)j; };
+    // the last of the visits it, it + g, .., it + k g that exists (it does)
+    auto last_visit = [&](uint32_t it, uint32_t k) -> uint32_t {
+        uint32_t r = it;
+        for (uint32_t q = 1; q <= k; ++q) r = it + q * g < a.n_tiles ? it + q * g : r;
+        return r;
+    };
+    // row tile rt of matrix mat of the forward's record of (tile, sample s); on = false: nothing is read
+    auto load_saved = [&](uint32_t tile, uint32_t s, int mat, int rt, bool on, f32x8 (&v)[2]) {
+        if constexpr (CP) {
+            const uint32_t sc = s < a.M ? s : a.M - 1;
+            load_tile_rows(make_srd(a.saved, on ? a.saved_bytes : 0), mat, rt,
+                           (sc >> 5) * (uint32_t)(ACT_TILE_FLOATS * 4) + ((sc & 31u) + 32u * (uint32_t)h) * 16u, v);
+        } else {
+            load_tile_rows(make_srd(a.saved + (size_t)tile * ACT_TILE_FLOATS, on ? ACT_TILE_FLOATS * 4 : 0), mat, rt, lane16, v);
+        }
+    };
+    auto load_small = [&](uint32_t s, f32x8 (&v)[2]) {
+        const uint32_t off = s * 32u;
         const float4 p = buf_load16(small_srd, off, 0), q = buf_load16(small_srd, off, 16);
         v[0][0] = p.x, v[0][1] = p.y, v[0][2] = p.z, v[0][3] = p.w, v[0][4] = q.x, v[0][5] = q.y, v[0][6] = q.z, v[0][7] = q.w;
     };
@@ -1596,15 +1619,12 @@ __device__ __forceinline__ void w16t_role_a(const W16Args& a, const W16T<A>& lx,
     auto dh2_srd = [&](uint32_t tile) {
         return make_srd(a.dact + (size_t)tile * ACT_TILE_FLOATS, recompute_x ? 0 : ACT_TILE_FLOATS * 4);
     };
-    auto load_x = [&](uint32_t tile, float (&v)[3]) {
-        const uint32_t s_raw = tile * 32u + (uint32_t)j;
+    auto load_x = [&](uint32_t s_raw, float (&v)[3]) {
         const uint32_t off = (s_raw < a.M ? s_raw : a.M - 1) * 12u;
 #pragma unroll
         for (int d = 0; d < 3; ++d) v[d] = __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(x_srd, off, 4 * d, 0));
     };
-    auto e_srd = [&](uint32_t tile) {       // (every wave issues the same loads: see w16x_role_a)
-        return make_srd(a.saved + (size_t)tile * ACT_TILE_FLOATS, w < 2 ? ACT_TILE_FLOATS * 4 : 0);
-    };
+    // (rgb_emb, read by waves 0, 1: every wave issues the same loads, see w16x_role_a)
     auto put_e = [&](uint32_t xe, const float (&xv)[3]) {
         v8 e[P];
         w16x_e_step<A>(w, xv[0], xv[1], xv[2], h, e);
@@ -1614,15 +1634,19 @@ __device__ __forceinline__ void w16t_role_a(const W16Args& a, const W16T<A>& lx,
     f32x8 bX[2], bS[2], bH3[2], bE[2];
     float xn[3] = {0.f, 0.f, 0.f};
     uint32_t it = blockIdx.x, par = 0;
+    uint32_t sN = 0, sNN = 0, sP = 0;       // CP: the samples of the next tile, of the one after it, and of the one after that
     if (it < a.n_tiles) {
         const uint32_t t0 = w16_tile(a, it);
-        load_x(t0, xn);
+        const uint32_t s0 = samp(t0);
+        if constexpr (CP) sN = samp(w16_tile(a, last_visit(it, 1))), sNN = samp(w16_tile(a, last_visit(it, 2)));
+        load_x(s0, xn);
         load_tile_rows(dh2_srd(t0), 1, w, lane16, bX);
-        load_small(t0, bS);
-        load_tile_rows(act_srd(a.saved, t0), 2, w, lane16, bH3);
-        load_tile_rows(e_srd(t0), 1, 2 + (w & 1), lane16, bE);
+        load_small(s0, bS);
+        load_saved(t0, s0, 2, w, true, bH3);
+        load_saved(t0, s0, 1, 2 + (w & 1), w < 2, bE);
         put_e(lx.xe, xn);
-        load_x(w16_tile(a, it + gridDim.x < a.n_tiles ? it + gridDim.x : it), xn);
+        if constexpr (CP) load_x(sN, xn);
+        else load_x(samp(w16_tile(a, it + gridDim.x < a.n_tiles ? it + gridDim.x : it)), xn);
     }
     w16x_barrier();
 #pragma clang loop unroll(disable)
@@ -1630,6 +1654,8 @@ __device__ __forceinline__ void w16t_role_a(const W16Args& a, const W16T<A>& lx,
         const bool more = it + gridDim.x < a.n_tiles;
         const uint32_t nt = more ? w16_tile(a, it + gridDim.x) : w16_tile(a, it);
         const uint32_t xe = lx.xe + par * XE_B, xa = lx.xa + par * XA_B, xb = lx.xb + par * XB_B;
+        if constexpr (CP) sP = samp(w16_tile(a, last_visit(it, 3)));
+        else sN = samp(nt);
         v8 X[P][2];
         W16_TRACE_DECL;
         W16_MARK(0);
@@ -1669,7 +1695,8 @@ __device__ __forceinline__ void w16t_role_a(const W16Args& a, const W16T<A>& lx,
         W16_MARK(1);
         if (!TWO_BARRIERS) {
             if (more) put_e(lx.xe + (par ^ 1u) * XE_B, xn);
-            load_x(w16_tile(a, it + 2 * gridDim.x < a.n_tiles ? it + 2 * gridDim.x : it), xn);
+            if constexpr (CP) load_x(sNN, xn);
+            else load_x(samp(w16_tile(a, it + 2 * gridDim.x < a.n_tiles ? it + 2 * gridDim.x : it)), xn);
         }
         W16_FENCE();
         W16_MARK(2);
@@ -1706,7 +1733,8 @@ __device__ __forceinline__ void w16t_role_a(const W16Args& a, const W16T<A>& lx,
         W16_MARK(4);
         if (TWO_BARRIERS) {
             if (more) put_e(lx.xe, xn);
-            load_x(w16_tile(a, it + 2 * gridDim.x < a.n_tiles ? it + 2 * gridDim.x : it), xn);
+            if constexpr (CP) load_x(sNN, xn);
+            else load_x(samp(w16_tile(a, it + 2 * gridDim.x < a.n_tiles ? it + 2 * gridDim.x : it)), xn);
         }
         // ---- the four H1 column tiles (ready planes)
         {
@@ -1739,9 +1767,10 @@ __device__ __forceinline__ void w16t_role_a(const W16Args& a, const W16T<A>& lx,
         if (w < 2) w16t_small_block<A>(bE, lx.scr, ad, S, acc_r);                        // rgb_emb (waves 0, 1)
         else w16t_small_ready<A>(xb + (uint32_t)(3 + (w - 2)) * CT_B, ad, S, acc_r);     // e column tile w - 2 (waves 2, 3)
         W16_FENCE();
-        load_small(nt, bS);
-        load_tile_rows(act_srd(a.saved, nt), 2, w, lane16, bH3);
-        load_tile_rows(e_srd(nt), 1, 2 + (w & 1), lane16, bE);
+        load_small(sN, bS);
+        load_saved(nt, sN, 2, w, true, bH3);
+        load_saved(nt, sN, 1, 2 + (w & 1), w < 2, bE);
+        if constexpr (CP) sN = sNN, sNN = sP;
         W16_FENCE();
         W16_MARK(6);
         if (TWO_BARRIERS) w16x_barrier();
@@ -1786,7 +1815,7 @@ __device__ __forceinline__ void w16t_role_a(const W16Args& a, const W16T<A>& lx,
 // waves 4..7 (rt): d w_sdf0[rt][0..2] = dG3[rt]^T [sdf_emb | grid], d b_sdf0;  d w_pts0[rt][0..1] = dG1[rt]^T e, d b_pts0 (the
 // ones column).  Produces column tiles: rt 0, 1 -> sdf_emb 0, 1 and rt 2 -> grid, as planes in load layout; rt 3 -> e 0 and
 // e 1 from XE's operand planes (the one transposition left on the matrix pipe: 12 MFMAs per tile).
-template <int LAYOUT, typename A>
+template <int LAYOUT, typename A, bool CP>
 __device__ __forceinline__ void w16t_role_b(const W16Args& a, const W16T<A>& lx, const typename A::v8 (&I)[2], int rt, int lane) {
     typedef W16XL<A> L;
     typedef typename A::v8 v8;
@@ -1811,11 +1840,23 @@ __device__ __forceinline__ void w16t_role_b(const W16Args& a, const W16T<A>& lx,
     };
     const uint64_t feat_bytes = (uint64_t)a.M * N_GRID * 4;
     const srd_t feat_srd = make_srd(a.feat, feat_bytes > 0xffffffffull ? 0xffffffffu : (uint32_t)feat_bytes);
-    auto load_mine = [&](uint32_t tile) {
+    const uint32_t g = gridDim.x;
+    auto samp = [&](uint32_t tile) -> uint32_t { return CP ? a.lidx[tile * 32u + (uint32_t)j] : tile * 32u + (uint32_t)j; };
+    auto last_visit = [&](uint32_t it, uint32_t k) -> uint32_t {
+        uint32_t r = it;
+        for (uint32_t q = 1; q <= k; ++q) r = it + q * g < a.n_tiles ? it + q * g : r;
+        return r;
+    };
+    auto load_mine = [&](uint32_t tile, uint32_t s_raw) {
         if (rt < 2) {
-            load_tile_rows(make_srd(a.saved + (size_t)tile * ACT_TILE_FLOATS, ACT_TILE_FLOATS * 4), 1, rt & 1, lane16, bY);
+            if constexpr (CP) {
+                const uint32_t sc = s_raw < a.M ? s_raw : a.M - 1;
+                load_tile_rows(make_srd(a.saved, a.saved_bytes), 1, rt & 1,
+                               (sc >> 5) * (uint32_t)(ACT_TILE_FLOATS * 4) + ((sc & 31u) + 32u * (uint32_t)h) * 16u, bY);
+            } else {
+                load_tile_rows(make_srd(a.saved + (size_t)tile * ACT_TILE_FLOATS, ACT_TILE_FLOATS * 4), 1, rt & 1, lane16, bY);
+            }
         } else if (rt == 2) {
-            const uint32_t s_raw = tile * 32u + (uint32_t)j;
             const uint32_t s_c = s_raw < a.M ? s_raw : a.M - 1;
             const uint32_t voff = LAYOUT == MIPSF_FEAT_AOS ? s_c * (uint32_t)(N_GRID * 4) + 4u * (uint32_t)h : (s_c * 2u + (uint32_t)h) * 4u;
             const uint32_t lstride = LAYOUT == MIPSF_FEAT_AOS ? 8u : a.M * 8u;
@@ -1831,20 +1872,28 @@ __device__ __forceinline__ void w16t_role_b(const W16Args& a, const W16T<A>& lx,
     const srd_t small_srd = make_srd(a.dsmall, a.M * 32u);
     f32x8 bSm;
     uint2 bMk = make_uint2(0u, 0u);
-    auto load_lean = [&](uint32_t tile) {
-        const uint32_t off = (tile * 32u + (uint32_t)j) * 32u;
+    auto load_lean = [&](uint32_t tile, uint32_t s_raw) {
+        const uint32_t off = s_raw * 32u;
         const float4 p = buf_load16(small_srd, off, 0), q = buf_load16(small_srd, off, 16);
         bSm[0] = p.x, bSm[1] = p.y, bSm[2] = p.z, bSm[3] = p.w, bSm[4] = q.x, bSm[5] = q.y, bSm[6] = q.z, bSm[7] = q.w;
-        if (lean) bMk = a.masks[(size_t)tile * (MASK_TILE_WORDS / 2) + 64 + lane];
+        if constexpr (CP) {
+            const uint32_t sc = s_raw < a.M ? s_raw : a.M - 1;
+            if (lean) bMk = a.masks[(size_t)(sc >> 5) * (MASK_TILE_WORDS / 2) + 64 + ((sc & 31u) + 32u * (uint32_t)h)];
+        } else {
+            if (lean) bMk = a.masks[(size_t)tile * (MASK_TILE_WORDS / 2) + 64 + lane];
+        }
     };
     auto g3_srd = [&](uint32_t tile) {
         return make_srd(a.dact + (size_t)tile * ACT_TILE_FLOATS, lean ? 0 : ACT_TILE_FLOATS * 4);
     };
     uint32_t it = blockIdx.x, par = 0;
+    uint32_t sN = 0, sNN = 0;               // CP: the samples of the next tile and of the one after it
     if (it < a.n_tiles) {
         const uint32_t t0 = w16_tile(a, it);
-        load_mine(t0);
-        load_lean(t0);
+        const uint32_t s0 = samp(t0);
+        if constexpr (CP) sN = samp(w16_tile(a, last_visit(it, 1)));
+        load_mine(t0, s0);
+        load_lean(t0, s0);
         load_tile_rows(g3_srd(t0), 2, rt, lane16, bG3);
         load_tile_rows(act_srd(a.dact, t0), 0, rt, lane16, bG1);
     }
@@ -1879,7 +1928,7 @@ __device__ __forceinline__ void w16t_role_b(const W16Args& a, const W16T<A>& lx,
         w16t_x32<A>(bG3, lx.scr, ad, X3);
         W16_FENCE();
         if (with_loads) {
-            load_lean(nt);
+            load_lean(nt, sN);
             load_tile_rows(g3_srd(nt), 2, rt, lane16, bG3);
         }
         W16_FENCE();
@@ -1895,7 +1944,7 @@ __device__ __forceinline__ void w16t_role_b(const W16Args& a, const W16T<A>& lx,
         W16_FENCE();
     };
     auto load_x = [&](uint32_t nt) {
-        load_lean(nt);
+        load_lean(nt, sN);
         load_tile_rows(g3_srd(nt), 2, rt, lane16, bG3);
         load_tile_rows(act_srd(a.dact, nt), 0, rt, lane16, bG1);
     };
@@ -1904,6 +1953,8 @@ __device__ __forceinline__ void w16t_role_b(const W16Args& a, const W16T<A>& lx,
     for (; it < a.n_tiles; it += gridDim.x, par ^= (L::NBUF == 2 ? 1u : 0u)) {
         const uint32_t nt = it + gridDim.x < a.n_tiles ? w16_tile(a, it + gridDim.x) : w16_tile(a, it);
         const uint32_t xe = lx.xe + par * XE_B, xb = lx.xb + par * XB_B;
+        if constexpr (CP) sNN = samp(w16_tile(a, last_visit(it, 2)));
+        else sN = samp(nt);
         W16_TRACE_DECL;
         W16_MARK(0);
         // ---- this wave's column tile(s) -> XB
@@ -1927,7 +1978,7 @@ __device__ __forceinline__ void w16t_role_b(const W16Args& a, const W16T<A>& lx,
             }
         }
         W16_FENCE();
-        load_mine(nt);
+        load_mine(nt, sN);
         W16_FENCE();
         W16_MARK(1);
         if (!EARLY_X) make_x(nt, true);
@@ -1949,6 +2000,7 @@ __device__ __forceinline__ void w16t_role_b(const W16Args& a, const W16T<A>& lx,
         if (EARLY_X && it + gridDim.x < a.n_tiles) make_x(0u, false);
         W16_MARK(6);
         if (TWO_BARRIERS) w16x_barrier();
+        if constexpr (CP) sN = sNN;
         W16_MARK(7);
         W16_TRACE_SUM(7, 4 + rt);
     }
@@ -1984,7 +2036,7 @@ __device__ __forceinline__ void w16t_role_b(const W16Args& a, const W16T<A>& lx,
 #define W16_TR 1            // experiments: 0 = the exchange form with matrix-core transposes (rounds 3-5)
 #endif
 
-template <int LAYOUT, typename A, bool RECOMP>
+template <int LAYOUT, typename A, bool RECOMP, bool CP = false>
 __global__ __launch_bounds__(W16_BLOCK, 2) void decoder_wgrad16_kernel(const float* __restrict__ packed16,
                                                                        const float* __restrict__ feat,
                                                                        const float* __restrict__ x,
@@ -1993,8 +2045,10 @@ __global__ __launch_bounds__(W16_BLOCK, 2) void decoder_wgrad16_kernel(const flo
                                                                        const float* __restrict__ dsmall,
                                                                        float* __restrict__ partial, uint32_t M,
                                                                        uint32_t n_tiles_all,
-                                                                       const uint32_t* __restrict__ live, uint32_t lean_dact) {
+                                                                       const uint32_t* __restrict__ live, uint32_t lean_dact,
+                                                                       const uint32_t* __restrict__ live_list, uint32_t saved_bytes) {
     const int tid = threadIdx.x, lane = tid & 63, w = __builtin_amdgcn_readfirstlane(tid >> 6);
+    if constexpr (CP) live = nullptr;         // compact mode: the compact tiles of live_list, counted in its header
     // live: the chain kernel's live-tile buffer (mipsf_decoder_bwd_chain16): eight lists, visited one after the other
     uint32_t n_tiles = n_tiles_all, live_start[8] = {0, 0, 0, 0, 0, 0, 0, 0};
     if (live) {
@@ -2005,6 +2059,7 @@ __global__ __launch_bounds__(W16_BLOCK, 2) void decoder_wgrad16_kernel(const flo
             n_tiles += (uint32_t)__builtin_amdgcn_readfirstlane((int)live[64 * q + 32]);
         }
     }
+    if constexpr (CP) n_tiles = (uint32_t)__builtin_amdgcn_readfirstlane((int)live_list[1]);
     const int j = lane & 31, h = lane >> 5;
     // the two selection matrices (B operands of the transposing MFMAs): lane = column c, half hb supplies k = 8 hb + u;
     // I[q][u] = 1 iff column c = 16 q + 8 (u >> 2) + 4 hb + (u & 3)
@@ -2057,13 +2112,15 @@ __global__ __launch_bounds__(W16_BLOCK, 2) void decoder_wgrad16_kernel(const flo
                         live_start[6], live_start[7]},
                        RECOMP ? w1img : nullptr, RECOMP ? w1img + W1_ENTRIES : nullptr,
                        (EXCH && lean_dact) ? gimg : nullptr,
-                       reinterpret_cast<const uint2*>(saved + (((size_t)M + 127) / 128) * 4 * ACT_TILE_FLOATS)};
+                       reinterpret_cast<const uint2*>(saved + (((size_t)M + 127) / 128) * 4 * ACT_TILE_FLOATS),
+                       CP ? live_list + MIPSF_LIVE_HEADER : nullptr, saved_bytes};
+    static_assert(!CP || (RECOMP && W16_EXCHANGE && W16_TR), "compact mode is built into the transpose-read exchange form only");
     if constexpr (TRF) {
         const uint32_t xb0 = w16t_lds_addr(xch);
         const W16T<A> lx = {xb0, xb0 + 16u * L::NBUF * L::XE, xb0 + 16u * L::NBUF * (L::XE + L::XA),
                             w16t_lds_addr(tscr) + (uint32_t)w * W16T_PLANE};
-        if (w < 4) w16t_role_a<LAYOUT, A>(a, lx, w, lane);
-        else w16t_role_b<LAYOUT, A>(a, lx, I, w - 4, lane);
+        if (w < 4) w16t_role_a<LAYOUT, A, CP>(a, lx, w, lane);
+        else w16t_role_b<LAYOUT, A, CP>(a, lx, I, w - 4, lane);
     } else if constexpr (EXCH) {
         typename A::v8* xp = reinterpret_cast<typename A::v8*>(xch);
         const W16X<A> lx = {xp, xp + L::NBUF * L::XE, xp + L::NBUF * (L::XE + L::XA)};
@@ -2105,6 +2162,7 @@ extern "C" int mipsf_decoder_wgrad16(const mipsf_decoder_wgrad16_args* a, void* 
     const float* saved = a->saved; const float* dact = a->dact; const uint32_t* tile_live = a->tile_live;
     const mipsf_decoder_grads* grads = a->grads; float* partial = a->partial; const int arithmetic = a->arithmetic;
     const uint32_t flags = a->flags, M = a->M;
+    const uint32_t* live_list = a->live_list;
     MIPSF_REQUIRE(packed16 == nullptr || a->packed16_floats == 0u || a->packed16_floats == decoder_packed16_floats(arithmetic),
                   "packed16 holds %u floats, arithmetic %d needs %u: packed for the other family?", a->packed16_floats, arithmetic,
                   (unsigned)decoder_packed16_floats(arithmetic));
@@ -2122,6 +2180,16 @@ extern "C" int mipsf_decoder_wgrad16(const mipsf_decoder_wgrad16_args* a, void* 
     MIPSF_REQUIRE(M < (1u << 25), "M = %u: the grid features are addressed through one 4 GB buffer resource", M);
     hipStream_t s = (hipStream_t)stream;
     const bool det = (flags & MIPSF_WGRAD_DETERMINISTIC) != 0u;
+    const uint64_t saved_bytes = (((uint64_t)M + 127) / 128) * 4 * ACT_TILE_FLOATS * 4;
+    if (live_list != nullptr) {
+        MIPSF_REQUIRE(packed16 != nullptr && (arithmetic == MIPSF_PREC_F16X3 || arithmetic == MIPSF_PREC_BF16X6) && W16_EXCHANGE && W16_TR,
+                      "a live-sample list is read by the transpose-read exchange form only (f16x3 / bf16x6 with packed16)");
+        // (MIPSF_WGRAD_DETERMINISTIC: the list is ascending whatever the schedule and compact tiles are visited in a fixed order,
+        // so nothing is put in order here; the reduce below is the ordered one)
+        MIPSF_REQUIRE(saved_bytes < (1ull << 32), "a live-sample list: the forward's record of %llu bytes is addressed through one "
+                      "buffer resource of less than 4 GiB", (unsigned long long)saved_bytes);
+        tile_live = nullptr;
+    }
     if (det && tile_live)         // (the caller's buffer: the lists are reordered in place, members and counts kept)
         if (int e = decoder_tile_lists_order(const_cast<uint32_t*>(tile_live), M, s)) return e;
     const uint32_t n_tiles = (uint32_t)(((uint64_t)M + 31) / 32);
@@ -2133,12 +2201,20 @@ extern "C" int mipsf_decoder_wgrad16(const mipsf_decoder_wgrad16_args* a, void* 
     if (blocks > (uint32_t)W16_MAX_BLOCKS) blocks = (uint32_t)W16_MAX_BLOCKS;
     const uint32_t* live = tile_live;
 #define W16(LAY, AR, RC) hipLaunchKernelGGL((decoder_wgrad16_kernel<LAY, AR, RC>), dim3(blocks), dim3(W16_BLOCK), 0, s, packed16, \
-                                            feat, x, saved, dact, dsmall, partial, M, n_tiles, live, lean_dact)
-#define W16_L(LAY) do { if (arithmetic == MIPSF_PREC_F16X3) { if (packed16) W16(LAY, ArF16, true); else W16(LAY, ArF16, false); } \
+                                            feat, x, saved, dact, dsmall, partial, M, n_tiles, live, lean_dact, live_list, (uint32_t)saved_bytes)
+#if W16_EXCHANGE && W16_TR
+#define W16C(LAY, AR) hipLaunchKernelGGL((decoder_wgrad16_kernel<LAY, AR, true, true>), dim3(blocks), dim3(W16_BLOCK), 0, s, packed16, \
+                                         feat, x, saved, dact, dsmall, partial, M, n_tiles, live, lean_dact, live_list, (uint32_t)saved_bytes)
+#else
+#define W16C(LAY, AR) ((void)0)          // (experiment builds of the other forms: the list was refused above)
+#endif
+#define W16_L(LAY) do { if (live_list) { if (arithmetic == MIPSF_PREC_F16X3) W16C(LAY, ArF16); else W16C(LAY, ArBF3); }    \
+                        else if (arithmetic == MIPSF_PREC_F16X3) { if (packed16) W16(LAY, ArF16, true); else W16(LAY, ArF16, false); } \
                         else if (arithmetic == MIPSF_PREC_BF16X6) { if (packed16) W16(LAY, ArBF3, true); else W16(LAY, ArBF3, false); } \
                         else W16(LAY, ArBF2, false); } while (0)
     if (feat_layout == MIPSF_FEAT_AOS) W16_L(MIPSF_FEAT_AOS); else W16_L(MIPSF_FEAT_LEVEL_MAJOR);
 #undef W16_L
+#undef W16C
 #undef W16
     if (int e = check_launch("decoder_wgrad16")) return e;
     return wgrad_reduce_launch(partial, blocks, grads, s, det);

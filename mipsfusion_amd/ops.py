@@ -76,12 +76,26 @@ def hashgrid_fwd(x: torch.Tensor, params: torch.Tensor, meta, layout=FEAT_AOS, w
     return out
 
 
+class LiveList:
+    """The live-sample list of a compacted ``decoder_bwd`` (mipsf_decoder_live_compact, include/mipsf.h), as its `tiles` value:
+    ``hashgrid_dx_from_jac(..., tiles=)`` then runs one thread per listed sample.  buf: the int32 buffer (header, entries)."""
+    __slots__ = ("buf",)
+
+    def __init__(self, buf):
+        self.buf = buf
+
+
 def hashgrid_dx_from_jac(jac, dout, dx, meta, layout=FEAT_AOS, tiles=None):
-    """dx += J . dout with the Jacobian saved by hashgrid_fwd(with_jac=True).  tiles: the live-tile lists that
+    """dx += J . dout with the Jacobian saved by hashgrid_fwd(with_jac=True).  tiles: the live-tile lists (or the LiveList) that
     ``decoder_bwd(..., return_tiles=True)`` hands back together with THIS `dout` -- the samples of the other tiles have a
     zero gradient and are left out (their Jacobian is not read).  Only pass lists that describe `dout` as it is now: a
     gradient added into `dout` afterwards (a feature regulariser, say) makes them stale -- leave `tiles` out then."""
     M = dx.shape[0]
+    if isinstance(tiles, LiveList):
+        with _timed("hashgrid_dx"):
+            check(lib().mipsf_hashgrid_dx_from_jac_list(dptr(jac), dptr(dout), dptr(dx), dptr(tiles.buf, torch.int32), M,
+                                                        C.byref(meta), layout, stream_ptr()), "hashgrid_dx_from_jac_list")
+        return
     with _timed("hashgrid_dx"):
         check(lib().mipsf_hashgrid_dx_from_jac(dptr(jac), dptr(dout), dptr(dx), dptr(tiles, torch.int32), M,
                                                C.byref(meta), layout, stream_ptr()), "hashgrid_dx_from_jac")
@@ -91,15 +105,21 @@ _SIDE_STREAMS = {}
 # decoder_bwd: short-cut the 32-sample tiles whose incoming gradient is zero throughout (exact; MIPSF_NO_TILE_SKIP=1 keeps
 # every tile, for A/B measurements)
 SKIP_ZERO_TILES = os.environ.get("MIPSF_NO_TILE_SKIP", "0") != "1"
-_LAST_TILE_LIVE = None          # (buffer, M) of the most recent decoder_bwd that used the short cut (reporting only)
+_LAST_TILE_LIVE = None          # (buffer, M, compacted) of the most recent decoder_bwd that used the short cut (reporting only)
+# decoder_bwd: pack the live samples into dense 32-sample tiles for the chain, the weight gradients and dx (exact for dfeat / dx;
+# the weight gradients regroup their fp32 sums; MIPSF_NO_COMPACT=1 keeps the live-tile lists, for A/B measurements)
+COMPACT_LIVE = os.environ.get("MIPSF_NO_COMPACT", "0") != "1"
 
 
 def last_live_tile_share() -> Optional[float]:
-    """Share of the 32-sample tiles the most recent ``decoder_bwd`` found to carry a gradient (None: no such call yet).
-    Reads the counts of the chain kernel's live-tile lists (words 64 q + 32, csrc/decoder16.hip); synchronises."""
+    """Share of the 32-sample tiles the most recent ``decoder_bwd`` worked on (None: no such call yet): the tiles it found to
+    carry a gradient (the counts of the chain kernel's live-tile lists, words 64 q + 32, csrc/decoder16.hip), or, when it
+    compacted the live samples, the compact tiles (word 1 of the live-sample list) over all tiles.  Synchronises."""
     if _LAST_TILE_LIVE is None:
         return None
-    buf, M = _LAST_TILE_LIVE
+    buf, M, compacted = _LAST_TILE_LIVE
+    if compacted:
+        return float(buf[1].item()) / max(1, (M + 31) // 32)
     counts = buf[32:512:64].cpu()
     return float(counts.sum().item()) / max(1, (M + 31) // 32)
 
@@ -407,8 +427,13 @@ def decoder_bwd(packed, feat, layout, x, embed_pos, out, dout, saved, grads, M, 
     Zero tiles (SKIP_ZERO_TILES, f16x3 chain with the streaming weight-gradient kernel or a frozen decoder): 32-sample
     tiles whose incoming gradient is zero throughout -- the ray tails behind the truncation band, a third of a mapping
     batch -- are flagged by the chain, get zero dfeat / dx, and are never touched by the weight-gradient kernel.
-    return_tiles: a 4th return value, the chain's live-tile lists (or None when no short cut was taken), for
-    ``hashgrid_dx_from_jac(..., tiles=)``.
+    Compaction (COMPACT_LIVE, on top of the zero-tile short cut; split precision, the exchange form of the streaming kernel
+    -- recompute_h1 with packed16 -- or a frozen decoder): a pre-pass lists the samples with a non-zero
+    incoming gradient in ascending order and writes the zeros of the others; chain, weight gradients and dx then work on
+    dense tiles of 32 listed samples.  dfeat and dx are bit-identical; the weight gradients regroup their fp32 sums
+    (deterministic: the list is ascending whatever the schedule, so the compacted call needs no ordering of tile lists).
+    return_tiles: a 4th return value, the chain's live-tile lists, the LiveList of a compacted call, or None when no short cut
+    was taken, for ``hashgrid_dx_from_jac(..., tiles=)``.
     deterministic: the streaming weight-gradient kernel runs with MIPSF_WGRAD_DETERMINISTIC: the live-tile lists are put in
     ascending order before it reads them (the chain fills them in the order its tiles finish, and the kernel's sums follow
     the list order) and its per-workgroup records are summed in a fixed order (the default reduce meets in float atomics).
@@ -431,6 +456,7 @@ def decoder_bwd(packed, feat, layout, x, embed_pos, out, dout, saved, grads, M, 
     dact = None if (grads is None and precision in SPLIT_PRECISIONS) else torch.empty(_lib.buffer_size(_lib.SIZE_DECODER_DACT, M), dtype=torch.float32, device=dev)
     pe_mode = 0 if embed_pos is None else 1
     tile_live = None
+    live_list = None
     lean_dact = False
     if precision in SPLIT_PRECISIONS:
         if embed_pos is not None or packed16 is None:
@@ -449,8 +475,16 @@ def decoder_bwd(packed, feat, layout, x, embed_pos, out, dout, saved, grads, M, 
                 pre[1] = False                      # (a second backward through the same record clears them itself)
             else:
                 tile_live = torch.empty(_lib.buffer_size(_lib.SIZE_DECODER_TILE_WORDS, M), dtype=torch.int32, device=dev)
-            _LAST_TILE_LIVE = (tile_live, M)
-        a = _lib.DecoderChain16Args.new(M=M, packed16=dptr(packed16), x=dptr(x), out=dptr(out), dout=dptr(dout), saved=dptr(saved),
+            _LAST_TILE_LIVE = (tile_live, M, False)
+            exchange = wgrad_precision == "stream_" + precision and recompute_h1 and packed16 is not None
+            if (COMPACT_LIVE and (grads is None or exchange)
+                    and _lib.buffer_size(_lib.SIZE_DECODER_SAVED, M) * 4 < (1 << 32)):
+                live_list = torch.empty(_lib.buffer_size(_lib.SIZE_DECODER_LIVE_LIST, M), dtype=torch.int32, device=dev)
+                _LAST_TILE_LIVE = (live_list, M, True)
+                with _timed("decoder_bwd_chain"):
+                    check(lib().mipsf_decoder_live_compact(dptr(dout), M, dptr(live_list, torch.int32), dptr(dfeat), dptr(dx),
+                                                           layout, stream_ptr()), "decoder_live_compact")
+        a = _lib.DecoderChain16Args.new(live_list=dptr(live_list, torch.int32), M=M, packed16=dptr(packed16), x=dptr(x), out=dptr(out), dout=dptr(dout), saved=dptr(saved),
                                         dfeat=dptr(dfeat), dx=dptr(dx), dact=dptr(dact), tile_live=dptr(tile_live, torch.int32),
                                         feat_layout=layout, flags=hdr_clear | (2 if lean_dact else 0), packed16_floats=packed16.numel())
         with _timed("decoder_bwd_chain"):
@@ -460,6 +494,7 @@ def decoder_bwd(packed, feat, layout, x, embed_pos, out, dout, saved, grads, M, 
             check(lib().mipsf_decoder_bwd_chain(dptr(packed), layout, dptr(x), pe_mode, dptr(out), dptr(dout),
                                                 dptr(saved), dptr(dfeat), dptr(dx), dptr(dpe), dptr(dact), M,
                                                 stream_ptr()), "decoder_bwd_chain")
+    tiles = LiveList(live_list) if live_list is not None else tile_live
     if grads is not None:
         partial = torch.empty(_lib.buffer_size(_lib.SIZE_DECODER_WGRAD_PARTIAL), dtype=torch.float32, device=dev)
         st = _decoder_struct(grads, _lib.DecoderGrads)
@@ -472,7 +507,8 @@ def decoder_bwd(packed, feat, layout, x, embed_pos, out, dout, saved, grads, M, 
                 raise RuntimeError("recompute_h1 needs wgrad_precision 'stream_f16x3' / 'stream_bf16x6' and packed16")
             if recompute_h1:
                 _check_family(packed16, wgrad_precision[len("stream_"):])
-            a = _lib.DecoderWgrad16Args.new(M=M, packed16=dptr(packed16) if recompute_h1 else None, feat=dptr(feat), x=dptr(x),
+            a = _lib.DecoderWgrad16Args.new(live_list=dptr(live_list, torch.int32),
+                                            M=M, packed16=dptr(packed16) if recompute_h1 else None, feat=dptr(feat), x=dptr(x),
                                             saved=dptr(saved), dact=dptr(dact), tile_live=dptr(tile_live, torch.int32),
                                             grads=C.pointer(st), partial=dptr(partial), feat_layout=layout, arithmetic=arith,
                                             flags=(_lib.WGRAD_LEAN_DACT if lean_dact else 0)
@@ -480,7 +516,7 @@ def decoder_bwd(packed, feat, layout, x, embed_pos, out, dout, saved, grads, M, 
                                             packed16_floats=packed16.numel() if recompute_h1 else 0)
             with _timed("decoder_wgrad"):
                 check(lib().mipsf_decoder_wgrad16(C.byref(a), stream_ptr()), "decoder_wgrad16")
-            return (dfeat, dx, dpe, tile_live) if return_tiles else (dfeat, dx, dpe)
+            return (dfeat, dx, dpe, tiles) if return_tiles else (dfeat, dx, dpe)
         if recompute_h1:
             raise RuntimeError("recompute_h1 needs wgrad_precision 'stream_f16x3'")
         if deterministic:
@@ -491,7 +527,7 @@ def decoder_bwd(packed, feat, layout, x, embed_pos, out, dout, saved, grads, M, 
             check(lib().mipsf_decoder_wgrad(dptr(feat), layout, dptr(x), dptr(embed_pos), pe_mode, dptr(saved),
                                             dptr(dact), C.byref(st), dptr(partial), wprec, M, stream_ptr()),
                   "decoder_wgrad")
-    return (dfeat, dx, dpe, tile_live) if return_tiles else (dfeat, dx, dpe)
+    return (dfeat, dx, dpe, tiles) if return_tiles else (dfeat, dx, dpe)
 
 
 def decoder_fwd_sdf(packed, feat, layout, x, embed_pos, M, precision: str = "f32", packed16=None) -> torch.Tensor:
