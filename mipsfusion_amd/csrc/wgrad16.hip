@@ -1,11 +1,12 @@
-// Decoder weight gradients on the 16-bit matrix cores.  THREE forms live in this file; which one a launch takes:
+// Decoder weight gradients on the 16-bit matrix cores.  TWO forms live in this file; which one a launch takes:
 //   * behind the lean records (packed16 given: H1 recomputed; the default of the Python modules), f16x3 and bf16x6:
-//       the TRANSPOSE-READ form (round 6, w16t_role_a / w16t_role_b, far below): operands several waves need are prepared
-//       once per tile and handed over through LDS, every transposition is an LDS write + ds_read_b64_tr_b16, the small-row
-//       products run on v_mfma_f32_16x16x32.  -DW16_TR=0 builds its predecessor, the EXCHANGE form with matrix-core
-//       transposes (rounds 3-5, w16x_role_a / w16x_role_b) -- kept as the A/B baseline of DESIGN.md 4.7;
-//   * full records (packed16 null) and the two-plane bf16 arithmetic: the STREAMING form described next (round 2,
-//       w16_role_a / w16_role_b): no LDS, no barriers, the matrix cores do the transposes.
+//       the TRANSPOSE-READ form of the exchange design (w16t_role_a / w16t_role_b, second half of the file): operands several
+//       waves need are prepared once per tile and handed over through LDS, every transposition but one is an LDS write +
+//       ds_read_b64_tr_b16, the small-row products run on v_mfma_f32_16x16x32.  The only form with the lean gradient record
+//       and with compact mode (a live-sample list);
+//   * full records (packed16 null) and the two-plane bf16 arithmetic: the STREAMING form described next (w16_role_a /
+//       w16_role_b): no LDS, one barrier per tile that only keeps the waves together, the matrix cores do the transposes.
+// (DESIGN.md 4.7 has the measurements, also against the forms that were removed from this file.)
 //
 // The streaming form:
 //
@@ -256,7 +257,7 @@ struct W16Args {
     const uint32_t* live;               // the live-tile buffer of the chain kernel (decoder16.hip), or null = every tile
     uint32_t live_cap;                  // capacity of one of its eight lists
     uint32_t live_start[8];             // first visit index of each list
-    const h8* w1_hi;                    // LDS copies of the forward's layer-1 operand images (recompute variant: P planes of
+    const h8* w1_hi;                    // LDS copies of the forward's layer-1 operand images (lean record: P planes of
     const h8* w1_lo;                    // RT_F1 x T16_F1 x 64 entries each, plane 0 first), else null
     // lean gradient record (MIPSF_WGRAD_LEAN_DACT, exchange form only): dG3 and the rgb_emb half of dH2 are recomputed
     const h8* gimg;                     // LDS: [S2T hi: 4 row tiles][S2T lo: 4][RGBT hi: 2][RGBT lo: 2] x 64 operands, or null
@@ -392,12 +393,10 @@ __device__ __forceinline__ void w16_role_a(const W16Args& a, const typename A::v
 #pragma clang loop unroll(disable)
     for (; it < a.n_tiles; it += gridDim.x) {
         const uint32_t tile = w16_tile(a, it);
-#ifndef W16_NO_TILE_BARRIER
         // The 8 waves read each other's records (H1 by all of waves 0..3, H2 by waves 4..7 and 0, 1): kept within one tile
         // of each other, the second to fourth reader hits in L2; free-running, they drift apart by whole tiles and the
         // re-reads go back to memory.
         __builtin_amdgcn_s_barrier();
-#endif
         const srd_t sa = act_srd(a.saved, tile);
         const uint32_t nt = it + gridDim.x < a.n_tiles ? w16_tile(a, it + gridDim.x) : tile;
         typename A::v8 X[P][2];
@@ -485,171 +484,6 @@ __device__ __forceinline__ void w16_role_a(const W16Args& a, const typename A::v
     }
 }
 
-// Role A of the LEAN record (mipsf_decoder_fwd16: H1 is not stored).  H1 is RECOMPUTED, directly in the layout the product
-// wants: the forward evaluates H1^T = W1 e^T with the weight image as A operand; with the operands swapped the same
-// instruction yields H1 = e W1^T -- lane = feature, registers = 16 samples -- from the SAME image (an A-operand image of
-// W1's rows is a B-operand image of W1^T's columns) and the same e operands, products in the same order: the forward's H1,
-// bit for bit, 12 MFMAs per 32 features instead of a 4 KB load + 4 transposing MFMAs.  The images (hi + lo, 32 KB) sit in
-// LDS.  Every load of a tile has its own buffer and is issued a whole tile ahead.
-template <int LAYOUT, typename A>
-__device__ __forceinline__ void w16_role_a_recompute(const W16Args& a, const typename A::v8 (&I)[2], int w, int lane) {
-    static_assert(A::SCALED && A::P == 2, "f16 hi/lo arithmetic only");
-    const int j = lane & 31, h = lane >> 5;
-    const uint32_t lane16 = 16u * (uint32_t)lane;
-    f32x16 acc[5];
-#pragma unroll
-    for (int t = 0; t < 5; ++t) zero_tile(acc[t]);
-    float bsum = 0.f, bsmall = 0.f, dummy = 0.f;
-    int k_main = 0, k_small = 0;
-    auto act_srd = [&](const float* recs, uint32_t tile) {
-        return make_srd(recs + (size_t)tile * ACT_TILE_FLOATS, ACT_TILE_FLOATS * 4);
-    };
-    const srd_t small_srd = make_srd(a.dsmall, a.M * 32u), x_srd = make_srd(a.x, a.M * 12u);
-    auto load_small = [&](uint32_t tile, f32x8 (&v)[2]) {
-        const uint32_t off = h == 0 ? (tile * 32u + (uint32_t)j) * 32u : 0xfffffff0u;
-        const float4 p = buf_load16(small_srd, off, 0), q = buf_load16(small_srd, off, 16);
-        v[0][0] = p.x, v[0][1] = p.y, v[0][2] = p.z, v[0][3] = p.w, v[0][4] = q.x, v[0][5] = q.y, v[0][6] = q.z, v[0][7] = q.w;
-    };
-    auto load_x = [&](uint32_t tile, float (&v)[3]) {
-        const uint32_t s_raw = tile * 32u + (uint32_t)j;
-        const uint32_t off = (s_raw < a.M ? s_raw : a.M - 1) * 12u;
-#pragma unroll
-        for (int d = 0; d < 3; ++d) v[d] = __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(x_srd, off, 4 * d, 0));
-    };
-    f32x8 bX[2], bS[2], bH3[2], bE[2];
-    float xv[3];
-    uint32_t it = blockIdx.x;
-    if (it < a.n_tiles) {
-        const uint32_t t0 = w16_tile(a, it);
-        load_tile_rows(act_srd(a.dact, t0), 1, w, lane16, bX);
-        load_x(t0, xv);
-        load_small(t0, bS);
-        load_tile_rows(act_srd(a.saved, t0), 2, w, lane16, bH3);
-        load_tile_rows(act_srd(a.saved, t0), 1, 2 + (w & 1), lane16, bE);
-    }
-#pragma clang loop unroll(disable)
-    for (; it < a.n_tiles; it += gridDim.x) {
-        const uint32_t tile = w16_tile(a, it);
-#ifndef W16_NO_TILE_BARRIER
-        __builtin_amdgcn_s_barrier();
-#endif
-        const uint32_t nt = it + gridDim.x < a.n_tiles ? w16_tile(a, it + gridDim.x) : tile;
-        const srd_t nsa = act_srd(a.saved, nt);
-        const float x0 = xv[0], x1 = xv[1], x2 = xv[2];
-        typename A::v8 X[2][2];
-        // ---- the small-row products first: their three buffers are free again before the long H1 phase starts
-        f32x8 sv1[2], sv2[2];
-        {
-            float rs;
-            const float sx = w16_pick_scale(w16_block_max_bits(bS, 1), k_small, rs);
-            if (rs != 1.0f) acc[4] *= rs, bsmall *= rs;
-            bS[0] *= sx;
-        }
-        sv1[0] = bS[0], sv2[0] = bS[0], sv1[1] = bS[0], sv2[1] = bS[0];
-        transpose_block<A, true, 1>(sv1, I, X, bsmall);                             // X = small rows (columns 0..11)
-        W16_FENCE();
-        transpose_mac<A>(bH3, I, X, acc[4]);                                        // H3[w] -> rows 0..15
-        transpose_block<A, false, 1>(sv2, I, X, dummy, 1);                          // the small rows at columns 16..27
-        W16_FENCE();
-        if (w < 2) {
-            transpose_mac<A>(bE, I, X, acc[4]);                                     // rgb_emb (waves 0, 1)
-        } else {
-            f32x8 ev[2];
-            if (w == 2) w16_e_tile<0>(x0, x1, x2, h, ev);
-            else w16_e_tile<1>(x0, x1, x2, h, ev);
-            transpose_mac<A>(ev, I, X, acc[4]);                                     // e (waves 2, 3)
-        }
-        W16_FENCE();
-        // ---- X = dH2[w]
-        {
-            float rs;
-            const float sx = w16_pick_scale(w16_block_max_bits(bX, 2), k_main, rs);
-            if (rs != 1.0f) {
-#pragma unroll
-                for (int t = 0; t < 4; ++t) acc[t] *= rs;
-                bsum *= rs;
-            }
-            bX[0] *= sx, bX[1] *= sx;
-        }
-        transpose_block<A, true>(bX, I, X, bsum);
-        W16_FENCE();
-        // ---- e as the forward's layer-1 operand: 4 k-steps of 8 slots per half, bias ones in slots 26, 27
-        typename A::v8 eh[4], el[4];
-#pragma unroll
-        for (int t = 0; t < 4; ++t) {            // one k-step at a time (pinned: 24 interleaved sines need 60 temporaries)
-            f32x8 ev;
-            if (t < 3) {
-                const float xd = t == 0 ? x0 : (t == 1 ? x1 : x2);
-#pragma unroll
-                for (int k = 0; k < 8; ++k) ev[k] = sin_reduced(fmaf(ldexpf(xd, k), PI_F, h ? HALF_PI_F : 0.0f));
-            } else {
-#pragma unroll
-                for (int k = 0; k < 8; ++k) ev[k] = 0.0f;
-                ev[0] = h ? x1 : x0, ev[1] = h ? 0.0f : x2;                  // slots 24, 25: the raw coordinates
-                ev[BIAS16_U] = 1.0f, ev[BIAS16_U + 1] = 1.0f;                // slots 26, 27 meet the bias halves of the image
-            }
-            eh[t] = next_plane<A, false>(ev), el[t] = next_plane<A, true>(ev);
-            asm volatile("" : "+v"(eh[t]), "+v"(el[t]));
-            W16_FENCE();
-        }
-        // the next tile's small-row operands have the whole H1 phase to arrive
-        load_small(nt, bS);
-        load_tile_rows(nsa, 2, w, lane16, bH3);
-        load_tile_rows(nsa, 1, 2 + (w & 1), lane16, bE);
-        W16_FENCE();
-        // ---- H1 column tiles, recomputed, multiplied at once
-        const f32x16 zero = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-        for (int ct = 0; ct < 4; ++ct) {
-            f32x16 hacc = zero;
-#pragma unroll
-            for (int t = 0; t < 4; ++t) {
-                const h8 wh = a.w1_hi[(ct * T16H_F1 + t) * 64 + lane], wl = a.w1_lo[(ct * T16_F1 + t) * 64 + lane];
-                hacc = mfma16(eh[t], wh, hacc);
-                hacc = mfma16(el[t], wh, hacc);
-                hacc = mfma16(eh[t], wl, hacc);
-            }
-#pragma unroll
-            for (int m = 0; m < 2; ++m) {                   // (k-step by k-step: one pair of operand planes alive)
-                f32x8 r;
-#pragma unroll
-                for (int u = 0; u < 8; ++u)
-                    r[u] = __builtin_amdgcn_fmed3f(hacc[8 * m + u] * (1.0f / (float)(1 << W16_SHIFT)), 0.0f, __builtin_inff());
-                const typename A::v8 yh = next_plane<A, false>(r);
-                const typename A::v8 yl = next_plane<A, true>(r);
-                acc[ct] = mfma16(X[0][m], yh, acc[ct]);
-                acc[ct] = mfma16(X[1][m], yh, acc[ct]);
-                acc[ct] = mfma16(X[0][m], yl, acc[ct]);
-            }
-            W16_FENCE();
-        }
-        // the next tile's dH2 and coordinates: needed after its small-row stages
-        load_tile_rows(act_srd(a.dact, nt), 1, w, lane16, bX);
-        load_x(nt, xv);
-        W16_FENCE();
-    }
-    float* rec = a.rec;
-#pragma unroll
-    for (int ct = 0; ct < 4; ++ct)
-        flush_mapped(rec, G_W_PTS2, HID, lane, acc[ct], w16_unscale(k_main), [&](int i) { return 32 * w + i; }, [&](int c) { return 32 * ct + c; });
-    flush_mapped(rec, G_W_SDF2, HID, lane, acc[4], w16_unscale(k_small),
-                 [&](int i) { const int r = w16_small_row(i); return r < N_CLASS ? r : -1; }, [&](int c) { return 32 * w + c; });
-    auto rgb_row = [&](int i) { const int r = i >= 16 ? w16_small_row(i - 16) : -1; return r >= N_CLASS ? r - N_CLASS : -1; };
-    if (w < 2)
-        flush_mapped(rec, G_W_RGB0, N_RGB_IN, lane, acc[4], w16_unscale(k_small), rgb_row, [&](int c) { return 32 * w + c; });
-    else
-        flush_mapped(rec, G_W_RGB0, N_RGB_IN, lane, acc[4], w16_unscale(k_small), rgb_row,
-                     [&](int c) { const int e = w16_e_col(w - 2, c); return e >= 0 ? N_EMB + e : -1; });
-    const float b2 = (bsum + __shfl_xor(bsum, 32, 64)) * w16_unscale(k_main);
-    if (h == 0) rec[G_B_PTS2 + 32 * w + j] = b2;
-    if (w == 0) {
-        const float bs = (bsmall + __shfl_xor(bsmall, 32, 64)) * w16_unscale(k_small);
-        const int r = w16_small_row(j);
-        if (h == 0 && r >= 0 && r < N_CLASS) rec[G_B_SDF2 + r] = bs;
-        if (h == 0 && r >= N_CLASS) rec[G_B_RGB0 + r - N_CLASS] = bs;
-    }
-}
-
 // waves 4..7 (row tile rt): d w_sdf0[rt][0..2] = dG3[rt]^T [sdf_emb | grid], d b_sdf0;  d w_pts0[rt][0..1] = dG1[rt]^T e,
 // d b_pts0 (e recomputed from x)
 template <int LAYOUT, typename A>
@@ -698,9 +532,7 @@ __device__ __forceinline__ void w16_role_b(const W16Args& a, const typename A::v
 #pragma clang loop unroll(disable)
     for (; it < a.n_tiles; it += gridDim.x) {
         const uint32_t tile = w16_tile(a, it);
-#ifndef W16_NO_TILE_BARRIER
-        __builtin_amdgcn_s_barrier();
-#endif
+        __builtin_amdgcn_s_barrier();       // (w16_role_a: the waves stay within one tile of each other)
         const srd_t sa = act_srd(a.saved, tile), da = act_srd(a.dact, tile);
         const uint32_t nt = it + gridDim.x < a.n_tiles ? w16_tile(a, it + gridDim.x) : tile;
         typename A::v8 X[P][2];
@@ -769,19 +601,46 @@ __device__ __forceinline__ void w16_role_b(const W16Args& a, const typename A::v
 }
 
 
-// ============================================================================ the EXCHANGE form (lean record, f16 hi/lo)
-// In the roles above every wave prepares all the operands its products need, and most of them are needed by four waves:
-// the four H1 column tiles (each of waves 0..3 recomputed all four: 48 of its ~100 MFMAs), the [sdf_emb | grid] and e
-// column tiles (transposed by each of waves 4..7), and the positional encoding itself (24 sines per lane, evaluated by all
-// eight waves).  Per SIMD and tile that came to 1504 vector + 158 matrix instructions; the kernel was bound by instruction
+// ====================================================== the TRANSPOSE-READ form (lean record; f16 hi/lo and bf16 three planes)
+// In the roles above every wave prepares all the operands its products need, and most of them are needed by four waves: the
+// four H1 column tiles, the [sdf_emb | grid] and e column tiles, and the positional encoding itself (24 sines per lane,
+// evaluated by all eight waves).  Done that way behind the lean record -- each of waves 0..3 recomputing all four H1 tiles: 48
+// of its ~100 MFMAs -- a SIMD and tile came to 1504 vector + 158 matrix instructions, and the kernel was bound by instruction
 // issue (~110 us at the 1.5 GHz the device sustains under this load, 141 us measured), not by its 0.4 GB of reads.
-// Here every shared operand is prepared ONCE per tile, by one wave, and handed to the others through LDS as ready MFMA
-// operand planes (16-byte pieces, lane-linear: conflict-free writes and reads), two buffers in rotation, ONE barrier per tile:
-//     XE  e as the forward's layer-1 operand: k-step t (hi, lo) by wave t          (for tile i + 1, written during tile i)
-//     XA  H1 column tile ct as the product's right-hand planes (yh0, yh1, yl0, yl1) by wave ct
-//     XB  transposed column tiles: sdf_emb 0, sdf_emb 1 (waves 4, 5), grid (wave 6), e 0, e 1 (wave 7, from XE's planes)
-// before the barrier a wave produces, transposes its own gradient blocks (unique to it) and reads nothing of this tile's
-// XA / XB; after it, it multiplies.
+// Here every shared operand is prepared ONCE per tile, by one wave, and handed to the others through LDS in 16-byte pieces
+// (conflict-free writes and reads):
+//     XE  e as the forward's layer-1 operand: k-step t (P planes) by wave t        (for tile i + 1, written during tile i)
+//     XA  H1 column tile ct as the product's right-hand operand planes, ready to use, by wave ct
+//     XB  column tiles: sdf_emb 0, sdf_emb 1 (waves 4, 5) and grid (wave 6) as planes in the records' LOAD layout, which the
+//         consumers read transposed; e 0, e 1 (wave 7, transposed from XE's planes on the matrix pipe) as ready planes
+// Before a tile's barrier a wave produces, prepares its own gradient blocks (unique to it) and reads nothing of this tile's
+// XA / XB; after it, it multiplies (how many buffers and barriers a tile takes: at W16XL below).
+// H1 is not in the lean record (mipsf_decoder_fwd16 does not store it).  It is RECOMPUTED, directly in the layout the product
+// wants: the forward evaluates H1^T = W1 e^T with the weight image as A operand; with the operands swapped the same instruction
+// yields H1 = e W1^T -- lane = feature, registers = 16 samples -- from the SAME image (an A-operand image of W1's rows is a
+// B-operand image of W1^T's columns) and the same e operands, products in the same order: the forward's H1, bit for bit, for
+// 4 P (P + 1) / 2 MFMAs per 32 features instead of a 4 KB load and a transposition.  The images (P planes of 16 KB) sit in LDS.
+//
+// Every other transposition is done by gfx950's LDS on the way out.  The streaming form gives it to the matrix pipe -- T = X I,
+// 2 MFMAs + 16 converts back to 16 bits per plane of a 32 x 32 block; handing operands over with such transposes took 162 of
+// 830 MFMAs per tile.  ds_read_b64_tr_b16 hands lane i of a 16-lane group element (i & 3) of the four 8-byte chunks that lanes
+// 4 k + (i >> 2) of the group address, k = 0..3 (tools/micro/tr_probe.hip checks the mapping on the device).  A block is cut
+// into its 16-bit planes in the records' LOAD layout (lane = sample, 16 features per lane as four chunks of four consecutive
+// features), every plane is written to LDS as it is cut (2 x ds_write_b128 per lane) and read back as the MFMA operand: lane =
+// feature, 8 consecutive samples per lane = two transpose reads of 4 samples each.
+//   plane of a block (2 KB): row = sample (64 B), four 16-byte slots; the lane (j, h) of the load layout owns slots
+//       (2 q + h) ^ sw(j), q = 0, 1 (features 16 q + 4 h + {0..3} and 16 q + 8 + 4 h + {0..3}: the two chunks of a slot),
+//       sw(j) = bit 1 of j | (bit 2 ^ bit 3 of j) << 1:  the 8 lanes of a ds_write_b128 group hit 8 different bank quads, the
+//       32 lanes of a transpose read cover 4 whole rows (32-wide operand) or complementary halves of 8 rows (16-wide operand)
+//       = all 64 banks once.
+// The small-row products (d w_sdf2: 5 rows, d w_rgb0: 3 rows; 0.7 % of the arithmetic, but 96 MFMAs of 32 x 32 x 16 + 60
+// transposing ones per tile when done like the streaming form's) run on v_mfma_f32_16x16x32: its k = 32 is the whole tile's
+// samples, 16 output rows hold the 8 small rows, and a product is one instruction of half the cycles per 16 columns.
+// Bias gradients: d b_pts0 and the small rows' are columns of products that exist anyway (the e operand carries constant
+// ones against the layer-1 bias pieces: column 18 of its second column tile); d b_pts2 / d b_sdf0 are per-lane sums in the
+// load layout, reduced across lanes once per launch.
+// Per tile (bf16, lean gradient record): 4 x (24 + 48 + 24 half-size) + 2 x 6 + 4 x (60 + 6) + 12 = 672 MFMA instructions.
+
 #ifdef W16_TRACE     // diagnosis builds (tools/micro/wgrad_probe.py): cycles between the marks of a tile, summed per wave
 __device__ unsigned long long w16_trace[2048 * 16];
 #define W16_MARK(k) do { __builtin_amdgcn_sched_barrier(0); tr_t[k] = __builtin_amdgcn_s_memtime(); __builtin_amdgcn_sched_barrier(0); } while (0)
@@ -841,14 +700,16 @@ __device__ __forceinline__ f32x16 w16x_narrow(const typename A::v8* img, int ent
     }
     return acc;
 }
-// LDS layout of the exchange form, in 16-byte entries (P planes):
+// LDS layout of the hand-over, in 16-byte entries (P planes):
 //   gimg   the chain's two narrow products' operand images: S2T plane p, row tile rt at (4 p + rt) x 64; RGBT plane p, row tile
 //          q at (4 P + 2 p + q) x 64
 //   XE     e as the forward's layer-1 operand: k-step t, plane p at (t P + p) x 64
-//   XA/XB  column tile ct: plane p, k-step m at (ct 2 P + 2 p + m) x 64
-// P = 2 (f16 hi / lo): every hand-over buffer exists TWICE (tile parity) and a tile needs ONE barrier; 134 KB.  P = 3 (bf16):
-// 201 KB that way -- single buffers and a SECOND barrier at the end of a tile instead (132 KB): XE for the next tile is then
-// written in the multiply phase, behind the first barrier.
+//   XA/XB  column tile ct at ct x CT: ready planes as plane p, k-step m at (2 p + m) x 64; load-layout planes as plane p at
+//          p x 128 (W16T_PLANE bytes each) -- P planes of 2 KB either way
+// P = 2 (f16 hi / lo): every hand-over buffer exists TWICE (tile parity) and a tile needs ONE barrier.  P = 3 (bf16): that would
+// be 214 KB of the CU's 160 -- single buffers and a SECOND barrier at the end of a tile instead: XE for the next tile is then
+// written in the multiply phase, behind the first barrier.  Either way 148 KB with the layer-1 images (P x 16) and one 2 KB
+// plane of scratch per wave: P = 2: 32 + 12 (gimg) + 2 x (8 + 16 + 20) + 16; P = 3: 48 + 18 + (12 + 24 + 30) + 16.
 template <typename A>
 struct W16XL {
     static constexpr int P = A::P;
@@ -856,13 +717,6 @@ struct W16XL {
     static constexpr int G_PLANE_S2T = 4 * 64, G_RGBT = 4 * P * 64, G_PLANE_RGBT = 2 * 64;
     static constexpr int XE = 4 * P * 64, XA = 4 * 2 * P * 64, XB = 5 * 2 * P * 64, CT = 2 * P * 64;
     static constexpr int NBUF = P == 3 ? 1 : 2;
-};
-
-template <typename A>
-struct W16X {
-    typename A::v8* xe;      // [NBUF][4 k-steps][P planes][64 lanes]
-    typename A::v8* xa;      // [NBUF][4 column tiles][2 P][64]
-    typename A::v8* xb;      // [NBUF][5 blocks][2 P][64]
 };
 
 // all LDS writes of this wave done, then the workgroup barrier (NOT __syncthreads: that also waits for every outstanding
@@ -896,497 +750,7 @@ __device__ __forceinline__ void w16x_e_step(int t, float x0, float x1, float x2,
     for (int p = 0; p < A::P; ++p) e[p] = p == A::P - 1 ? next_plane<A, true>(ev) : next_plane<A, false>(ev);
 }
 
-// acc += X^T Y for ready planes: y = one column tile of XA / XB (plane pb, k-step m at (2 pb + m) x 64); the plane pairs with
-// pa + pb <= P - 1, k-step by k-step
-template <typename A>
-__device__ __forceinline__ void w16x_mac(const typename A::v8 (&X)[A::P][2], const typename A::v8* y, int lane, f32x16& acc) {
-#ifdef W16_DBG_NO_COMPUTE
-    return;
-#endif
-    constexpr int P = A::P;
-    typename A::v8 Y[P][2];
-#pragma unroll
-    for (int pb = 0; pb < P; ++pb)
-#pragma unroll
-        for (int m = 0; m < 2; ++m) Y[pb][m] = y[(2 * pb + m) * 64 + lane];
-#pragma unroll
-    for (int m = 0; m < 2; ++m)
-#pragma unroll
-        for (int pb = 0; pb < P; ++pb)
-#pragma unroll
-            for (int pa = 0; pa + pb < P; ++pa) acc = mfma16(X[pa][m], Y[pb][m], acc);
-}
-// two such products side by side (acc_a += Xa^T Ya, acc_b += Xb^T Yb), their MFMAs in turn: a chain of MFMAs on ONE
-// accumulator issues every ~82 cycles instead of every 32 (each waits for the one in front of it); with two chains per wave
-// and two waves per SIMD the matrix pipe always finds an independent instruction
-template <typename A>
-__device__ __forceinline__ void w16x_mac2(const typename A::v8 (&Xa)[A::P][2], const typename A::v8* ya, f32x16& acc_a,
-                                          const typename A::v8 (&Xb)[A::P][2], const typename A::v8* yb, f32x16& acc_b, int lane) {
-#ifdef W16_DBG_NO_COMPUTE
-    return;
-#endif
-    constexpr int P = A::P;
-#pragma unroll
-    for (int m = 0; m < 2; ++m)
-#pragma unroll
-        for (int pb = 0; pb < P; ++pb) {
-            const typename A::v8 Ya = ya[(2 * pb + m) * 64 + lane], Yb = yb[(2 * pb + m) * 64 + lane];
-#pragma unroll
-            for (int pa = 0; pa + pb < P; ++pa) {
-                acc_a = mfma16(Xa[pa][m], Ya, acc_a);
-                acc_b = mfma16(Xb[pa][m], Yb, acc_b);
-            }
-        }
-}
-template <typename A>
-__device__ __forceinline__ void w16x_put(typename A::v8* y, int lane, const typename A::v8 (&Y)[A::P][2]) {
-#pragma unroll
-    for (int p = 0; p < A::P; ++p)
-#pragma unroll
-        for (int m = 0; m < 2; ++m) y[(2 * p + m) * 64 + lane] = Y[p][m];
-}
-
-// waves 0..3 (w): d w_pts2[w][0..3] = dH2[w]^T H1, d b_pts2; rows 0..15 of the fifth tile (small rows)^T H3[w] -> d w_sdf2,
-// rows 16..31 (small rows)^T {rgb_emb 0 | rgb_emb 1 | e 0 | e 1}[w] -> d w_rgb0.  Produces e k-step w and H1 column tile w.
-template <int LAYOUT, typename A>
-__device__ __forceinline__ void w16x_role_a(const W16Args& a, const W16X<A>& lx, const typename A::v8 (&I)[2], int w, int lane) {
-    typedef W16XL<A> L;
-    typedef typename A::v8 v8;
-    constexpr int P = A::P;
-    constexpr bool TWO_BARRIERS = L::NBUF == 1;
-    const int j = lane & 31, h = lane >> 5;
-    const uint32_t lane16 = 16u * (uint32_t)lane;
-    f32x16 acc[5];
-#pragma unroll
-    for (int t = 0; t < 5; ++t) zero_tile(acc[t]);
-    float bsum = 0.f, bsmall = 0.f, dummy = 0.f;
-    int k_main = 0, k_small = 0;
-    auto act_srd = [&](const float* recs, uint32_t tile) {
-        return make_srd(recs + (size_t)tile * ACT_TILE_FLOATS, ACT_TILE_FLOATS * 4);
-    };
-    const srd_t small_srd = make_srd(a.dsmall, a.M * 32u), x_srd = make_srd(a.x, a.M * 12u);
-    // small rows: BOTH halves read their sample's 8 values (the recomputation below scales by the sample); only half 0's copy
-    // enters the small-row products (the other half's lanes contribute zeros)
-    auto load_small = [&](uint32_t tile, f32x8 (&v)[2]) {
-        const uint32_t off = (tile * 32u + (uint32_t)j) * 32u;
-        const float4 p = buf_load16(small_srd, off, 0), q = buf_load16(small_srd, off, 16);
-        v[0][0] = p.x, v[0][1] = p.y, v[0][2] = p.z, v[0][3] = p.w, v[0][4] = q.x, v[0][5] = q.y, v[0][6] = q.z, v[0][7] = q.w;
-    };
-    const v8* gimg = reinterpret_cast<const v8*>(a.gimg);
-    const v8* w1 = reinterpret_cast<const v8*>(a.w1_hi);     // [P planes][RT_F1 x T16_F1 x 64]
-    constexpr int W1_PLANE = RT_F1 * T16H_F1 * 64;
-    const bool recompute_x = a.gimg != nullptr && w >= 2;       // lean gradient record: dH2[2], dH2[3] = Wrgb^T drgb are not stored
-    auto dh2_srd = [&](uint32_t tile) {
-        return make_srd(a.dact + (size_t)tile * ACT_TILE_FLOATS, recompute_x ? 0 : ACT_TILE_FLOATS * 4);
-    };
-    auto load_x = [&](uint32_t tile, float (&v)[3]) {
-        const uint32_t s_raw = tile * 32u + (uint32_t)j;
-        const uint32_t off = (s_raw < a.M ? s_raw : a.M - 1) * 12u;
-#pragma unroll
-        for (int d = 0; d < 3; ++d) v[d] = __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(x_srd, off, 4 * d, 0));
-    };
-    // Every wave issues the SAME loads in the same order, whether it needs them or not (waves 2, 3 have no rgb_emb tile: their
-    // resource is empty, the loads return zeros without touching memory): the compiler counts outstanding loads per program
-    // path, and where paths with different counts meet it waits for the shortest one's count -- a wave on a longer path then
-    // waits for loads it has just issued (measured: 2700 instead of 900 cycles in the phase behind such a join).
-    auto e_srd = [&](uint32_t tile) {
-        return make_srd(a.saved + (size_t)tile * ACT_TILE_FLOATS, w < 2 ? ACT_TILE_FLOATS * 4 : 0);
-    };
-    auto put_e = [&](v8* xe, const float (&xv)[3]) {
-        v8 e[P];
-        w16x_e_step<A>(w, xv[0], xv[1], xv[2], h, e);
-#pragma unroll
-        for (int p = 0; p < P; ++p) xe[(w * P + p) * 64 + lane] = e[p];
-    };
-    f32x8 bX[2], bS[2], bH3[2], bE[2];
-    float xn[3] = {0.f, 0.f, 0.f};           // coordinates of the NEXT tile (its e is produced during this one)
-    uint32_t it = blockIdx.x, par = 0;
-    if (it < a.n_tiles) {
-        const uint32_t t0 = w16_tile(a, it);
-        load_x(t0, xn);
-        load_tile_rows(dh2_srd(t0), 1, w, lane16, bX);
-        load_small(t0, bS);
-        load_tile_rows(act_srd(a.saved, t0), 2, w, lane16, bH3);
-        load_tile_rows(e_srd(t0), 1, 2 + (w & 1), lane16, bE);
-        put_e(lx.xe, xn);
-        load_x(w16_tile(a, it + gridDim.x < a.n_tiles ? it + gridDim.x : it), xn);
-    }
-    w16x_barrier();
-#pragma clang loop unroll(disable)
-    for (; it < a.n_tiles; it += gridDim.x, par ^= (L::NBUF == 2 ? 1u : 0u)) {
-        const bool more = it + gridDim.x < a.n_tiles;
-        const uint32_t nt = more ? w16_tile(a, it + gridDim.x) : w16_tile(a, it);
-        v8* xe = lx.xe + par * L::XE;
-        v8* xa = lx.xa + par * L::XA;
-        const v8* xb = lx.xb + par * L::XB;
-        v8 X[P][2];
-        W16_TRACE_DECL;
-        W16_MARK(0);
-        // ---- H1 column tile w = e W1[w]^T (the operands swapped: lane = feature, registers = 16 samples; the forward's H1
-        //      bit for bit: the forward's products in the forward's order), ReLU, planes -> XA
-        {
-            f32x16 hacc = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-            for (int t = 0; t < 4; ++t) {
-#ifdef W16_DBG_NO_COMPUTE
-                break;
-#endif
-                v8 e[P], wp[P];
-#pragma unroll
-                for (int p = 0; p < P; ++p) e[p] = xe[(t * P + p) * 64 + lane], wp[p] = w1[p * W1_PLANE + (w * T16H_F1 + t) * 64 + lane];
-                hacc = mfma16(e[0], wp[0], hacc);
-                hacc = mfma16(e[1], wp[0], hacc);
-                if constexpr (P == 3) {
-                    hacc = mfma16(e[2], wp[0], hacc);
-                    hacc = mfma16(e[1], wp[1], hacc);
-                    hacc = mfma16(e[0], wp[1], hacc);
-                    hacc = mfma16(e[0], wp[2], hacc);
-                } else {
-                    hacc = mfma16(e[0], wp[1], hacc);
-                }
-            }
-            v8 Y[P][2];
-#pragma unroll
-            for (int m = 0; m < 2; ++m) {
-                f32x8 r;
-#pragma unroll
-                for (int u = 0; u < 8; ++u)
-                    r[u] = __builtin_amdgcn_fmed3f(hacc[8 * m + u] * w16_acc_unscale<A>(), 0.0f, __builtin_inff());
-#pragma unroll
-                for (int p = 0; p < P; ++p) Y[p][m] = p == P - 1 ? next_plane<A, true>(r) : next_plane<A, false>(r);
-            }
-            w16x_put<A>(xa + w * L::CT, lane, Y);
-        }
-        W16_FENCE();
-        W16_MARK(1);
-        // ---- e k-step w of the NEXT tile.  Two buffers: into the other one, now (it is read by everybody before the next
-        //      barrier).  One buffer: behind this tile's first barrier (below).
-        if (!TWO_BARRIERS) {
-            if (more) put_e(lx.xe + (par ^ 1u) * L::XE, xn);
-            load_x(w16_tile(a, it + 2 * gridDim.x < a.n_tiles ? it + 2 * gridDim.x : it), xn);
-        }
-        W16_FENCE();
-        W16_MARK(2);
-        // ---- X = dH2[w]
-        if (recompute_x) {          // = (Wrgb[:, :64]^T drgb)[row tile w - 2], as the chain kernel computed it
-            float up, down;
-            w16x_updown(bS[0], up, down);
-            v8 rp[P];
-            w16x_small_operand<A>(bS[0], N_CLASS, 3, up, h, rp);
-            const f32x16 ac = w16x_narrow<A>(gimg, L::G_RGBT + (w - 2) * 64 + lane, L::G_PLANE_RGBT, rp);
-            const float unscale = w16_acc_unscale<A>();
-#pragma unroll
-            for (int q = 0; q < 2; ++q)
-#pragma unroll
-                for (int u = 0; u < 8; ++u) bX[q][u] = (ac[8 * q + u] * unscale) * down;
-        }
-        if (A::SCALED) {
-            float rs;
-            const float sx = w16_pick_scale(w16_block_max_bits(bX, 2), k_main, rs);
-            if (rs != 1.0f) {
-#pragma unroll
-                for (int t = 0; t < 4; ++t) acc[t] *= rs;
-                bsum *= rs;
-            }
-            bX[0] *= sx, bX[1] *= sx;
-        }
-        transpose_block<A, true>(bX, I, X, bsum);
-        W16_FENCE();
-        load_tile_rows(dh2_srd(nt), 1, w, lane16, bX);                  // the next tile's dH2
-        W16_FENCE();
-        W16_MARK(3);
-        w16x_barrier();
-        W16_MARK(4);
-        if (TWO_BARRIERS) {         // everybody has read this tile's e: the next tile's goes into the same buffer
-            if (more) put_e(lx.xe, xn);
-            load_x(w16_tile(a, it + 2 * gridDim.x < a.n_tiles ? it + 2 * gridDim.x : it), xn);
-        }
-        // ---- the four H1 column tiles
-        if constexpr (P == 3) {
-            w16x_mac2<A>(X, xa, acc[0], X, xa + L::CT, acc[1], lane);
-            w16x_mac2<A>(X, xa + 2 * L::CT, acc[2], X, xa + 3 * L::CT, acc[3], lane);
-        } else {
-#pragma unroll
-            for (int ct = 0; ct < 4; ++ct) w16x_mac<A>(X, xa + ct * L::CT, lane, acc[ct]);
-        }
-        W16_FENCE();
-        W16_MARK(5);
-        // ---- small rows: (d logits, d rgb)^T H3[w] (rows 0..15), ^T {rgb_emb | e} (rows 16..31)
-        f32x8 sv1[2], sv2[2];
-        if (h != 0) {
-#pragma unroll
-            for (int u = 0; u < 8; ++u) bS[0][u] = 0.0f;
-        }
-        if (A::SCALED) {
-            float rs;
-            const float sx = w16_pick_scale(w16_block_max_bits(bS, 1), k_small, rs);
-            if (rs != 1.0f) acc[4] *= rs, bsmall *= rs;
-            bS[0] *= sx;
-        }
-        sv1[0] = bS[0], sv2[0] = bS[0], sv1[1] = bS[0], sv2[1] = bS[0];
-        transpose_block<A, true, 1>(sv1, I, X, bsmall);                             // X = small rows (columns 0..11)
-        W16_FENCE();
-        transpose_mac<A>(bH3, I, X, acc[4]);                                        // H3[w] -> rows 0..15
-        transpose_block<A, false, 1>(sv2, I, X, dummy, 1);                          // the small rows at columns 16..27
-        W16_FENCE();
-        if (w < 2) transpose_mac<A>(bE, I, X, acc[4]);                              // rgb_emb (waves 0, 1)
-        else w16x_mac<A>(X, xb + (3 + (w - 2)) * L::CT, lane, acc[4]);              // e column tile w - 2 (waves 2, 3)
-        W16_FENCE();
-        load_small(nt, bS);
-        load_tile_rows(act_srd(a.saved, nt), 2, w, lane16, bH3);
-        load_tile_rows(e_srd(nt), 1, 2 + (w & 1), lane16, bE);
-        W16_FENCE();
-        W16_MARK(6);
-        if (TWO_BARRIERS) w16x_barrier();      // this tile's XA / XB have been read: the next tile may overwrite them
-        W16_MARK(7);
-        W16_TRACE_SUM(7, w);
-    }
-    float* rec = a.rec;
-#pragma unroll
-    for (int ct = 0; ct < 4; ++ct)
-        flush_mapped(rec, G_W_PTS2, HID, lane, acc[ct], w16_unscale(k_main), [&](int i) { return 32 * w + i; }, [&](int c) { return 32 * ct + c; });
-    flush_mapped(rec, G_W_SDF2, HID, lane, acc[4], w16_unscale(k_small),
-                 [&](int i) { const int r = w16_small_row(i); return r < N_CLASS ? r : -1; }, [&](int c) { return 32 * w + c; });
-    auto rgb_row = [&](int i) { const int r = i >= 16 ? w16_small_row(i - 16) : -1; return r >= N_CLASS ? r - N_CLASS : -1; };
-    if (w < 2)
-        flush_mapped(rec, G_W_RGB0, N_RGB_IN, lane, acc[4], w16_unscale(k_small), rgb_row, [&](int c) { return 32 * w + c; });
-    else
-        flush_mapped(rec, G_W_RGB0, N_RGB_IN, lane, acc[4], w16_unscale(k_small), rgb_row,
-                     [&](int c) { const int e = w16_e_col(w - 2, c); return e >= 0 ? N_EMB + e : -1; });
-    const float b2 = (bsum + __shfl_xor(bsum, 32, 64)) * w16_unscale(k_main);
-    if (h == 0) rec[G_B_PTS2 + 32 * w + j] = b2;
-    if (w == 0) {
-        const float bs = (bsmall + __shfl_xor(bsmall, 32, 64)) * w16_unscale(k_small);
-        const int r = w16_small_row(j);
-        if (h == 0 && r >= 0 && r < N_CLASS) rec[G_B_SDF2 + r] = bs;
-        if (h == 0 && r >= N_CLASS) rec[G_B_RGB0 + r - N_CLASS] = bs;
-    }
-}
-
-// waves 4..7 (rt): d w_sdf0[rt][0..2] = dG3[rt]^T [sdf_emb | grid], d b_sdf0;  d w_pts0[rt][0..1] = dG1[rt]^T e, d b_pts0.
-// Produces the transposed column tiles: rt 0, 1 -> sdf_emb 0, 1; rt 2 -> grid; rt 3 -> e 0 and e 1 (from XE's planes).
-template <int LAYOUT, typename A>
-__device__ __forceinline__ void w16x_role_b(const W16Args& a, const W16X<A>& lx, const typename A::v8 (&I)[2], int rt, int lane) {
-    typedef W16XL<A> L;
-    typedef typename A::v8 v8;
-    constexpr int P = A::P;
-    constexpr bool TWO_BARRIERS = L::NBUF == 1;
-#ifndef W16_B_EARLY_X
-#define W16_B_EARLY_X 1      // experiments: 0 = both transposes between the second barrier and the first one (round 4's first form)
-#endif
-    constexpr bool EARLY_X = TWO_BARRIERS && W16_B_EARLY_X;
-    const int j = lane & 31, h = lane >> 5;
-    const uint32_t lane16 = 16u * (uint32_t)lane;
-    f32x16 acc[5];
-#pragma unroll
-    for (int t = 0; t < 5; ++t) zero_tile(acc[t]);
-    float bsum0 = 0.f, bsum1 = 0.f, dummy = 0.f;
-    int k3 = 0, k1 = 0;
-    f32x8 bG3[2], bG1[2], bY[2];
-    auto act_srd = [&](const float* recs, uint32_t tile) {
-        return make_srd(recs + (size_t)tile * ACT_TILE_FLOATS, ACT_TILE_FLOATS * 4);
-    };
-    const uint64_t feat_bytes = (uint64_t)a.M * N_GRID * 4;
-    const srd_t feat_srd = make_srd(a.feat, feat_bytes > 0xffffffffull ? 0xffffffffu : (uint32_t)feat_bytes);
-    // what this wave transposes for everybody: sdf_emb row tile rt for rt < 2 (4 loads of 16 bytes), the grid features for
-    // rt == 2 (16 loads of 4 bytes), both into bY -- the branch is wave-uniform, and the wave with the e column tiles (rt == 3)
-    // loads nothing here
-    auto load_mine = [&](uint32_t tile) {
-        if (rt < 2) {
-            load_tile_rows(make_srd(a.saved + (size_t)tile * ACT_TILE_FLOATS, ACT_TILE_FLOATS * 4), 1, rt & 1, lane16, bY);
-        } else if (rt == 2) {
-            const uint32_t s_raw = tile * 32u + (uint32_t)j;
-            const uint32_t s_c = s_raw < a.M ? s_raw : a.M - 1;
-            const uint32_t voff = LAYOUT == MIPSF_FEAT_AOS ? s_c * (uint32_t)(N_GRID * 4) + 4u * (uint32_t)h : (s_c * 2u + (uint32_t)h) * 4u;
-            const uint32_t lstride = LAYOUT == MIPSF_FEAT_AOS ? 8u : a.M * 8u;
-#pragma unroll
-            for (int q = 0; q < 2; ++q)
-#pragma unroll
-                for (int u = 0; u < 8; ++u)
-                    bY[q][u] = __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(feat_srd, voff, (uint32_t)(8 * q + u) * lstride, 0));
-        }
-    };
-    // lean gradient record: dG3[rt] = relu'(H3[rt]) (Ws2^T dlogits)[rt] is recomputed from the sample's 8 small-row values and
-    // its mask bits (loaded one tile ahead like everything else); the record's dG3 pieces are then read through an empty resource
-    const bool lean = a.gimg != nullptr;
-    const v8* gimg = reinterpret_cast<const v8*>(a.gimg);
-    const srd_t small_srd = make_srd(a.dsmall, a.M * 32u);
-    f32x8 bSm;
-    uint2 bMk = make_uint2(0u, 0u);
-    auto load_lean = [&](uint32_t tile) {
-        const uint32_t off = (tile * 32u + (uint32_t)j) * 32u;
-        const float4 p = buf_load16(small_srd, off, 0), q = buf_load16(small_srd, off, 16);
-        bSm[0] = p.x, bSm[1] = p.y, bSm[2] = p.z, bSm[3] = p.w, bSm[4] = q.x, bSm[5] = q.y, bSm[6] = q.z, bSm[7] = q.w;
-        if (lean) bMk = a.masks[(size_t)tile * (MASK_TILE_WORDS / 2) + 64 + lane];
-    };
-    auto g3_srd = [&](uint32_t tile) {
-        return make_srd(a.dact + (size_t)tile * ACT_TILE_FLOATS, lean ? 0 : ACT_TILE_FLOATS * 4);
-    };
-    uint32_t it = blockIdx.x, par = 0;
-    if (it < a.n_tiles) {
-        const uint32_t t0 = w16_tile(a, it);
-        load_mine(t0);
-        load_lean(t0);
-        load_tile_rows(g3_srd(t0), 2, rt, lane16, bG3);
-        load_tile_rows(act_srd(a.dact, t0), 0, rt, lane16, bG1);
-    }
-    w16x_barrier();
-    const f32x16 zero = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
-    v8 X3[P][2], X1[P][2];
-    // X3 = dG3[rt], X1 = dG1[rt] of the tile whose records are in bSm / bMk / bG3 / bG1, then the loads of tile `nt` into them
-    auto make_x = [&](uint32_t nt, bool with_loads) {
-        if (lean) {
-            float up, down;
-            w16x_updown(bSm, up, down);
-            v8 lp[P];
-            w16x_small_operand<A>(bSm, 0, N_CLASS, up, h, lp);
-            const f32x16 ac = w16x_narrow<A>(gimg, rt * 64 + lane, L::G_PLANE_S2T, lp);
-            const uint32_t m3[2] = {bMk.x, bMk.y};
-            const float unscale = w16_acc_unscale<A>();
-#pragma unroll
-            for (int q = 0; q < 2; ++q)
-#pragma unroll
-                for (int u = 0; u < 8; ++u) bG3[q][u] = mask_apply(m3, rt, 8 * q + u, ac[8 * q + u] * unscale) * down;
-        }
-        if (A::SCALED) {
-            float rs;
-            const float sx = w16_pick_scale(w16_block_max_bits(bG3, 2), k3, rs);
-            if (rs != 1.0f) {
-#pragma unroll
-                for (int t = 0; t < 3; ++t) acc[t] *= rs;
-                bsum0 *= rs;
-            }
-            bG3[0] *= sx, bG3[1] *= sx;
-        }
-        transpose_block<A, true>(bG3, I, X3, bsum0);
-        W16_FENCE();
-        if (with_loads) {
-            load_lean(nt);
-            load_tile_rows(g3_srd(nt), 2, rt, lane16, bG3);
-        }
-        W16_FENCE();
-        if (A::SCALED) {
-            float rs;
-            const float sx = w16_pick_scale(w16_block_max_bits(bG1, 2), k1, rs);
-            if (rs != 1.0f) acc[3] *= rs, acc[4] *= rs, bsum1 *= rs;
-            bG1[0] *= sx, bG1[1] *= sx;
-        }
-        transpose_block<A, true>(bG1, I, X1, bsum1);
-        W16_FENCE();
-        if (with_loads) load_tile_rows(act_srd(a.dact, nt), 0, rt, lane16, bG1);
-        W16_FENCE();
-    };
-    auto load_x = [&](uint32_t nt) {       // the records make_x reads, of tile nt
-        load_lean(nt);
-        load_tile_rows(g3_srd(nt), 2, rt, lane16, bG3);
-        load_tile_rows(act_srd(a.dact, nt), 0, rt, lane16, bG1);
-    };
-    // With ONE set of exchange buffers (P = 3: two sets do not fit the CU's LDS) a tile has two barriers, and everything a wave
-    // does between the second one and the first one of the next tile is on the workgroup's critical path (the role-a waves wait
-    // at the first barrier with their products still to do).  The two transposes of this role are private to the wave, so there
-    // they are done for the NEXT tile right behind this tile's products -- beside the role-a waves' products -- and only the
-    // column tile everybody waits for is left between the barriers (phase trace, tools/replay.py w16trace: the role-a waves
-    // waited 6 350 of their 15 960 cycles per tile at the first barrier).
-    if (EARLY_X && it < a.n_tiles) make_x(0u, false);
-#pragma clang loop unroll(disable)
-    for (; it < a.n_tiles; it += gridDim.x, par ^= (L::NBUF == 2 ? 1u : 0u)) {
-        const uint32_t nt = it + gridDim.x < a.n_tiles ? w16_tile(a, it + gridDim.x) : w16_tile(a, it);
-        const v8* xe = lx.xe + par * L::XE;
-        v8* xb = lx.xb + par * L::XB;
-        W16_TRACE_DECL;
-        W16_MARK(0);
-        // ---- this wave's column tile(s) -> XB
-        if (rt < 3) {
-            if (rt == 2) bY[0] = bY[0] * w16_grid_shift<A>(), bY[1] = bY[1] * w16_grid_shift<A>();
-            v8 Y[P][2];
-            transpose_block<A, false>(bY, I, Y, dummy);
-            w16x_put<A>(xb + rt * L::CT, lane, Y);
-        } else {
-#pragma unroll
-            for (int blk = 0; blk < 2; ++blk) {           // e column tile blk = k-steps 2 blk, 2 blk + 1, plane by plane
-                v8 Y[P][2];
-#pragma unroll
-                for (int pb = 0; pb < P; ++pb) {
-#ifdef W16_DBG_NO_COMPUTE
-                    Y[pb][0] = I[0], Y[pb][1] = I[1];
-                    continue;
-#endif
-                    f32x16 T = mfma16(xe[((2 * blk) * P + pb) * 64 + lane], I[0], zero);
-                    T = mfma16(xe[((2 * blk + 1) * P + pb) * 64 + lane], I[1], T);
-                    pack_T<A>(T, Y[pb]);
-                }
-                w16x_put<A>(xb + (3 + blk) * L::CT, lane, Y);
-            }
-        }
-        W16_FENCE();
-        load_mine(nt);
-        W16_FENCE();
-        W16_MARK(1);
-#ifndef W16_B_LOADS_LATE
-#define W16_B_LOADS_LATE 1           // experiments: 0 = the next records' loads in front of the first barrier
-#endif
-        if (!EARLY_X) make_x(nt, true);       // ---- X3 = dG3[rt], X1 = dG1[rt]
-        else if (!W16_B_LOADS_LATE) load_x(nt);
-        W16_MARK(2);
-        W16_MARK(3);
-        w16x_barrier();
-        W16_MARK(4);
-        // (the column tile's temporaries are gone, and issuing these loads is not in the other waves' way any more: the
-        // records of the next tile's X3, X1; the products below cover their latency)
-        if (EARLY_X && W16_B_LOADS_LATE) load_x(nt);
-        if constexpr (P == 3) {
-            w16x_mac2<A>(X3, xb, acc[0], X3, xb + L::CT, acc[1], lane);
-            w16x_mac2<A>(X3, xb + 2 * L::CT, acc[2], X1, xb + 3 * L::CT, acc[3], lane);
-            w16x_mac<A>(X1, xb + 4 * L::CT, lane, acc[4]);
-        } else {
-#pragma unroll
-            for (int ct = 0; ct < 3; ++ct) w16x_mac<A>(X3, xb + ct * L::CT, lane, acc[ct]);
-#pragma unroll
-            for (int ct = 0; ct < 2; ++ct) w16x_mac<A>(X1, xb + (3 + ct) * L::CT, lane, acc[3 + ct]);
-        }
-        W16_FENCE();
-        W16_MARK(5);
-        if (EARLY_X && it + gridDim.x < a.n_tiles) make_x(0u, false);      // the next tile's X3, X1
-        W16_MARK(6);
-        if (TWO_BARRIERS) w16x_barrier();
-        W16_MARK(7);
-        W16_TRACE_SUM(7, 4 + rt);
-    }
-    float* rec = a.rec;
-#pragma unroll
-    for (int ct = 0; ct < 2; ++ct)
-        flush_mapped(rec, G_W_SDF0, N_SDF_IN, lane, acc[ct], w16_unscale(k3), [&](int i) { return 32 * rt + i; }, [&](int c) { return 32 * ct + c; });
-    flush_mapped(rec, G_W_SDF0, N_SDF_IN, lane, acc[2], w16_unscale(k3) / w16_grid_shift<A>(), [&](int i) { return 32 * rt + i; },
-                 [&](int c) { return N_EMB + 2 * (8 * (c >> 4) + 4 * ((c >> 3) & 1) + (c & 3)) + ((c >> 2) & 1); });
-#pragma unroll
-    for (int ct = 0; ct < 2; ++ct)
-        flush_mapped(rec, G_W_PTS0, N_E, lane, acc[3 + ct], w16_unscale(k1), [&](int i) { return 32 * rt + i; },
-                     [&](int c) { return w16_e_col(ct, c); });
-    const float b3 = (bsum0 + __shfl_xor(bsum0, 32, 64)) * w16_unscale(k3), b1 = (bsum1 + __shfl_xor(bsum1, 32, 64)) * w16_unscale(k1);
-    if (h == 0) rec[G_B_SDF0 + 32 * rt + j] = b3, rec[G_B_PTS0 + 32 * rt + j] = b1;
-}
-
-
-// ============================================================ the TRANSPOSE-READ form (round 6): the exchange form without
-// matrix-core transposes.  What round 2 gave to the matrix pipe -- T = X I, 2 MFMAs + 16 converts back to 16 bits per plane of
-// a 32 x 32 block: 162 of the exchange form's 830 MFMAs per tile -- is what gfx950's LDS does on the way out:
-// ds_read_b64_tr_b16 hands lane i of a 16-lane group element (i & 3) of the four 8-byte chunks that lanes 4 k + (i >> 2) of
-// the group address, k = 0..3 (tools/micro/tr_probe.hip checks the mapping on the device).  A block is cut into its 16-bit
-// planes in the records' LOAD layout (lane = sample, 16 features per lane as four chunks of four consecutive features), every
-// plane is written to LDS as it is cut (2 x ds_write_b128 per lane) and read back as the MFMA operand: lane = feature, 8
-// consecutive samples per lane = two transpose reads of 4 samples each.
-//   plane of a block (2 KB): row = sample (64 B), four 16-byte slots; the lane (j, h) of the load layout owns slots
-//       (2 q + h) ^ sw(j), q = 0, 1 (features 16 q + 4 h + {0..3} and 16 q + 8 + 4 h + {0..3}: the two chunks of a slot),
-//       sw(j) = bit 1 of j | (bit 2 ^ bit 3 of j) << 1:  the 8 lanes of a ds_write_b128 group hit 8 different bank quads, the
-//       32 lanes of a transpose read cover 4 whole rows (32-wide operand) or complementary halves of 8 rows (16-wide operand)
-//       = all 64 banks once.
-// The small-row products (d w_sdf2: 5 rows, d w_rgb0: 3 rows; 96 MFMAs of 32 x 32 x 16 + 60 transposing ones per tile in the
-// exchange form, for 0.7 % of the arithmetic) run on v_mfma_f32_16x16x32: its k = 32 is the whole tile's samples, 16 output
-// rows hold the 8 small rows, and a product is one instruction of half the cycles per 16 columns.
-// Bias gradients: d b_pts0 and the small rows' are columns of products that exist anyway (the e operand carries constant
-// ones against the layer-1 bias pieces: column 18 of its second column tile); d b_pts2 / d b_sdf0 are per-lane sums in the
-// load layout, reduced across lanes once per launch.
-// Per tile: 4 x (24 + 48 + 24 half-size [+ 6]) + 4 x (60 [+ 6] [+ 12]) = 684 MFMA instructions (830), 612 in 32 x 32 units.
+// ---- the transposing LDS reads
 typedef short s4v __attribute__((ext_vector_type(4)));
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 #define W16_LDS(T, addr) ((__attribute__((address_space(3))) T*)(addr))
@@ -1485,7 +849,9 @@ struct W16YTr {
         return w16t_tr2<A>(b0 + o, b1 + o);
     }
 };
-// acc_a += Xa^T Ya, acc_b += Xb^T Yb, the two chains' MFMAs in turn (w16x_mac2)
+// acc_a += Xa^T Ya, acc_b += Xb^T Yb, the two chains' MFMAs in turn: a chain of MFMAs on ONE accumulator issues every ~82 cycles
+// instead of every 32 (each waits for the one in front of it); with two chains per wave and two waves per SIMD the matrix pipe
+// always finds an independent instruction
 template <typename A, typename YA, typename YB>
 __device__ __forceinline__ void w16t_mac2(const typename A::v8 (&Xa)[A::P][2], const YA& ya, f32x16& acc_a,
                                           const typename A::v8 (&Xb)[A::P][2], const YB& yb, f32x16& acc_b) {
@@ -1607,6 +973,8 @@ __device__ __forceinline__ void w16t_role_a(const W16Args& a, const W16T<A>& lx,
             load_tile_rows(make_srd(a.saved + (size_t)tile * ACT_TILE_FLOATS, on ? ACT_TILE_FLOATS * 4 : 0), mat, rt, lane16, v);
         }
     };
+    // small rows: BOTH halves read their sample's 8 values (the recomputation of dH2 below scales by the sample); only half 0's
+    // copy enters the small-row products (the other half's lanes contribute zeros)
     auto load_small = [&](uint32_t s, f32x8 (&v)[2]) {
         const uint32_t off = s * 32u;
         const float4 p = buf_load16(small_srd, off, 0), q = buf_load16(small_srd, off, 16);
@@ -1615,7 +983,7 @@ __device__ __forceinline__ void w16t_role_a(const W16Args& a, const W16T<A>& lx,
     const v8* gimg = reinterpret_cast<const v8*>(a.gimg);
     const v8* w1 = reinterpret_cast<const v8*>(a.w1_hi);
     constexpr int W1_PLANE = RT_F1 * T16H_F1 * 64;
-    const bool recompute_x = a.gimg != nullptr && w >= 2;
+    const bool recompute_x = a.gimg != nullptr && w >= 2;       // lean gradient record: dH2[2], dH2[3] = Wrgb^T drgb are not stored
     auto dh2_srd = [&](uint32_t tile) {
         return make_srd(a.dact + (size_t)tile * ACT_TILE_FLOATS, recompute_x ? 0 : ACT_TILE_FLOATS * 4);
     };
@@ -1624,7 +992,10 @@ __device__ __forceinline__ void w16t_role_a(const W16Args& a, const W16T<A>& lx,
 #pragma unroll
         for (int d = 0; d < 3; ++d) v[d] = __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(x_srd, off, 4 * d, 0));
     };
-    // (rgb_emb, read by waves 0, 1: every wave issues the same loads, see w16x_role_a)
+    // Every wave issues the SAME loads in the same order, whether it needs them or not (waves 2, 3 have no rgb_emb tile: their
+    // resource is empty, load_saved's `on`, and the loads return zeros without touching memory): the compiler counts outstanding
+    // loads per program path, and where paths with different counts meet it waits for the shortest one's count -- a wave on a
+    // longer path then waits for loads it has just issued (measured: 2700 instead of 900 cycles in the phase behind such a join).
     auto put_e = [&](uint32_t xe, const float (&xv)[3]) {
         v8 e[P];
         w16x_e_step<A>(w, xv[0], xv[1], xv[2], h, e);
@@ -1659,7 +1030,8 @@ __device__ __forceinline__ void w16t_role_a(const W16Args& a, const W16T<A>& lx,
         v8 X[P][2];
         W16_TRACE_DECL;
         W16_MARK(0);
-        // ---- H1 column tile w = e W1[w]^T, ReLU, planes -> XA (comes out of the product in operand layout: w16x_role_a)
+        // ---- H1 column tile w = e W1[w]^T (the operands swapped: lane = feature, registers = 16 samples; the forward's products
+        //      in the forward's order: its H1 bit for bit), ReLU, planes -> XA
         {
             f32x16 hacc = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
 #pragma unroll
@@ -1847,6 +1219,9 @@ __device__ __forceinline__ void w16t_role_b(const W16Args& a, const W16T<A>& lx,
         for (uint32_t q = 1; q <= k; ++q) r = it + q * g < a.n_tiles ? it + q * g : r;
         return r;
     };
+    // what this wave publishes for everybody: sdf_emb row tile rt for rt < 2 (4 loads of 16 bytes), the grid features for
+    // rt == 2 (16 loads of 4 bytes), both into bY -- the branch is wave-uniform, and the wave with the e column tiles (rt == 3)
+    // loads nothing here
     auto load_mine = [&](uint32_t tile, uint32_t s_raw) {
         if (rt < 2) {
             if constexpr (CP) {
@@ -1867,6 +1242,8 @@ __device__ __forceinline__ void w16t_role_b(const W16Args& a, const W16T<A>& lx,
                     bY[q][u] = __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(feat_srd, voff, (uint32_t)(8 * q + u) * lstride, 0));
         }
     };
+    // lean gradient record: dG3[rt] = relu'(H3[rt]) (Ws2^T dlogits)[rt] is recomputed from the sample's 8 small-row values and
+    // its mask bits (loaded one tile ahead like everything else); the record's dG3 pieces are then read through an empty resource
     const bool lean = a.gimg != nullptr;
     const v8* gimg = reinterpret_cast<const v8*>(a.gimg);
     const srd_t small_srd = make_srd(a.dsmall, a.M * 32u);
@@ -1900,6 +1277,7 @@ __device__ __forceinline__ void w16t_role_b(const W16Args& a, const W16T<A>& lx,
     w16x_barrier();
     const f32x16 zero = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
     v8 X3[P][2], X1[P][2];
+    // X3 = dG3[rt], X1 = dG1[rt] of the tile whose records are in bSm / bMk / bG3 / bG1, then the loads of tile `nt` into them
     auto make_x = [&](uint32_t nt, bool with_loads) {
         if (lean) {
             float up, down;
@@ -1943,11 +1321,18 @@ __device__ __forceinline__ void w16t_role_b(const W16Args& a, const W16T<A>& lx,
         if (with_loads) load_tile_rows(act_srd(a.dact, nt), 0, rt, lane16, bG1);
         W16_FENCE();
     };
-    auto load_x = [&](uint32_t nt) {
+    auto load_x = [&](uint32_t nt) {       // the records make_x reads, of tile nt
         load_lean(nt, sN);
         load_tile_rows(g3_srd(nt), 2, rt, lane16, bG3);
         load_tile_rows(act_srd(a.dact, nt), 0, rt, lane16, bG1);
     };
+    // With ONE set of hand-over buffers (P = 3) a tile has two barriers, and everything a wave does between the second one and
+    // the first one of the next tile is on the workgroup's critical path (the role-a waves wait at the first barrier with their
+    // products still to do).  The two transpositions of this role are private to the wave, so there they are done for the NEXT
+    // tile right behind this tile's products -- beside the role-a waves' products -- and only the column tile everybody waits
+    // for is left between the barriers (phase trace, tools/replay.py w16trace: before, the role-a waves waited 6 350 of their
+    // 15 960 cycles per tile at the first barrier).  The next records' loads follow the first barrier: the column tile's
+    // temporaries are gone by then, issuing them is not in the other waves' way any more, and the products cover their latency.
     if (EARLY_X && it < a.n_tiles) make_x(0u, false);
 #pragma clang loop unroll(disable)
     for (; it < a.n_tiles; it += gridDim.x, par ^= (L::NBUF == 2 ? 1u : 0u)) {
@@ -2029,12 +1414,6 @@ __device__ __forceinline__ void w16t_role_b(const W16Args& a, const W16T<A>& lx,
         }
 }
 
-#ifndef W16_EXCHANGE
-#define W16_EXCHANGE 1      // experiments: 0 = every wave prepares its own operands (the roles above) behind the lean record, too
-#endif
-#ifndef W16_TR
-#define W16_TR 1            // experiments: 0 = the exchange form with matrix-core transposes (rounds 3-5)
-#endif
 
 template <int LAYOUT, typename A, bool RECOMP, bool CP = false>
 __global__ __launch_bounds__(W16_BLOCK, 2) void decoder_wgrad16_kernel(const float* __restrict__ packed16,
@@ -2071,16 +1450,14 @@ __global__ __launch_bounds__(W16_BLOCK, 2) void decoder_wgrad16_kernel(const flo
             I[q][u] = (j == 16 * q + 8 * (u >> 2) + 4 * h + (u & 3)) ? (typename A::elt)1.0f : (typename A::elt)0.0f;
     constexpr int W1_ENTRIES = RT_F1 * T16H_F1 * 64;          // 16-byte operands of one layer-1 image (hi; lo has as many)
     static_assert(T16H_F1 == T16_F1, "layer 1 has no separate bias k-step");
-    constexpr bool EXCH = RECOMP && W16_EXCHANGE;
     typedef W16XL<A> L;
     constexpr int P = A::P;
+    constexpr int SCR_ENTRIES = 8 * (W16T_PLANE / 16);       // one plane of scratch per wave
     __shared__ h8 w1img[RECOMP ? P * W1_ENTRIES : 1];
-    __shared__ h8 xch[EXCH ? L::NBUF * (L::XE + L::XA + L::XB) : 1];
-    __shared__ h8 gimg[EXCH ? L::G_ENTRIES : 1];
-    constexpr bool TRF = EXCH && W16_TR;
-    __shared__ h8 tscr[TRF ? 8 * (W16T_PLANE / 16) : 1];          // transpose-read form: one plane of scratch per wave
-    static_assert(!EXCH || sizeof(h8) * (P * W1_ENTRIES + L::NBUF * (L::XE + L::XA + L::XB) + L::G_ENTRIES + (TRF ? 8 * (W16T_PLANE / 16) : 0))
-                               <= 160 * 1024,
+    __shared__ h8 xch[RECOMP ? L::NBUF * (L::XE + L::XA + L::XB) : 1];
+    __shared__ h8 gimg[RECOMP ? L::G_ENTRIES : 1];
+    __shared__ h8 tscr[RECOMP ? SCR_ENTRIES : 1];
+    static_assert(!RECOMP || sizeof(h8) * (P * W1_ENTRIES + L::NBUF * (L::XE + L::XA + L::XB) + L::G_ENTRIES + SCR_ENTRIES) <= 160 * 1024,
                   "the exchange form's images and hand-over buffers must fit the LDS of a CU");
     if constexpr (RECOMP) {
         // planes 0 and 1 of an image sit where the f16 layout has hi and lo; plane 2 (bf16 only) in the buffer's extension
@@ -2091,18 +1468,17 @@ __global__ __launch_bounds__(W16_BLOCK, 2) void decoder_wgrad16_kernel(const flo
             w1img[W1_ENTRIES + q] = img[(IMG16H_HALVES + OFF16L_F1) / 8 + q];
             if constexpr (P == 3) w1img[2 * W1_ENTRIES + q] = ext[(EXT16_FWD + OFF16L_F1) / 8 + q];
         }
-        if constexpr (EXCH) {       // the chain's two narrow products: operand images of the backward sets, plane by plane
-            const h8* bimg = img + OFF16_BWD_HALVES / 8;
-            for (int q = tid; q < 4 * 64; q += W16_BLOCK) {
-                gimg[q] = bimg[OFF16B_S2T / 8 + q];
-                gimg[L::G_PLANE_S2T + q] = bimg[(IMG16B_HALVES + OFF16B_S2T) / 8 + q];
-                if constexpr (P == 3) gimg[2 * L::G_PLANE_S2T + q] = ext[(EXT16_BWD + OFF16B_S2T) / 8 + q];
-            }
-            for (int q = tid; q < 2 * 64; q += W16_BLOCK) {
-                gimg[L::G_RGBT + q] = bimg[OFF16B_RGBT / 8 + q];
-                gimg[L::G_RGBT + L::G_PLANE_RGBT + q] = bimg[(IMG16B_HALVES + OFF16B_RGBT) / 8 + q];
-                if constexpr (P == 3) gimg[L::G_RGBT + 2 * L::G_PLANE_RGBT + q] = ext[(EXT16_BWD + OFF16B_RGBT) / 8 + q];
-            }
+        // the chain's two narrow products: operand images of the backward sets, plane by plane
+        const h8* bimg = img + OFF16_BWD_HALVES / 8;
+        for (int q = tid; q < 4 * 64; q += W16_BLOCK) {
+            gimg[q] = bimg[OFF16B_S2T / 8 + q];
+            gimg[L::G_PLANE_S2T + q] = bimg[(IMG16B_HALVES + OFF16B_S2T) / 8 + q];
+            if constexpr (P == 3) gimg[2 * L::G_PLANE_S2T + q] = ext[(EXT16_BWD + OFF16B_S2T) / 8 + q];
+        }
+        for (int q = tid; q < 2 * 64; q += W16_BLOCK) {
+            gimg[L::G_RGBT + q] = bimg[OFF16B_RGBT / 8 + q];
+            gimg[L::G_RGBT + L::G_PLANE_RGBT + q] = bimg[(IMG16B_HALVES + OFF16B_RGBT) / 8 + q];
+            if constexpr (P == 3) gimg[L::G_RGBT + 2 * L::G_PLANE_RGBT + q] = ext[(EXT16_BWD + OFF16B_RGBT) / 8 + q];
         }
         __syncthreads();
     }
@@ -2111,28 +1487,19 @@ __global__ __launch_bounds__(W16_BLOCK, 2) void decoder_wgrad16_kernel(const flo
                        {live_start[0], live_start[1], live_start[2], live_start[3], live_start[4], live_start[5],
                         live_start[6], live_start[7]},
                        RECOMP ? w1img : nullptr, RECOMP ? w1img + W1_ENTRIES : nullptr,
-                       (EXCH && lean_dact) ? gimg : nullptr,
+                       (RECOMP && lean_dact) ? gimg : nullptr,
                        reinterpret_cast<const uint2*>(saved + (((size_t)M + 127) / 128) * 4 * ACT_TILE_FLOATS),
                        CP ? live_list + MIPSF_LIVE_HEADER : nullptr, saved_bytes};
-    static_assert(!CP || (RECOMP && W16_EXCHANGE && W16_TR), "compact mode is built into the transpose-read exchange form only");
-    if constexpr (TRF) {
+    static_assert(!CP || RECOMP, "compact mode is built into the transpose-read exchange form only");
+    if constexpr (RECOMP) {         // the lean record: the transpose-read form; the full record: the streaming form
         const uint32_t xb0 = w16t_lds_addr(xch);
         const W16T<A> lx = {xb0, xb0 + 16u * L::NBUF * L::XE, xb0 + 16u * L::NBUF * (L::XE + L::XA),
                             w16t_lds_addr(tscr) + (uint32_t)w * W16T_PLANE};
         if (w < 4) w16t_role_a<LAYOUT, A, CP>(a, lx, w, lane);
         else w16t_role_b<LAYOUT, A, CP>(a, lx, I, w - 4, lane);
-    } else if constexpr (EXCH) {
-        typename A::v8* xp = reinterpret_cast<typename A::v8*>(xch);
-        const W16X<A> lx = {xp, xp + L::NBUF * L::XE, xp + L::NBUF * (L::XE + L::XA)};
-        if (w < 4) w16x_role_a<LAYOUT, A>(a, lx, I, w, lane);
-        else w16x_role_b<LAYOUT, A>(a, lx, I, w - 4, lane);
     } else {
-        if (w < 4) {
-            if constexpr (RECOMP) w16_role_a_recompute<LAYOUT, A>(a, I, w, lane);
-            else w16_role_a<LAYOUT, A>(a, I, w, lane);
-        } else {
-            w16_role_b<LAYOUT, A>(a, I, w - 4, lane);
-        }
+        if (w < 4) w16_role_a<LAYOUT, A>(a, I, w, lane);
+        else w16_role_b<LAYOUT, A>(a, I, w - 4, lane);
     }
 }
 
@@ -2169,7 +1536,7 @@ extern "C" int mipsf_decoder_wgrad16(const mipsf_decoder_wgrad16_args* a, void* 
     if (M == 0) return 0;
     MIPSF_REQUIRE((flags & ~(uint32_t)(MIPSF_WGRAD_LEAN_DACT | MIPSF_WGRAD_DETERMINISTIC)) == 0u, "unknown flags 0x%x", flags);
     const uint32_t lean_dact = (flags & MIPSF_WGRAD_LEAN_DACT) ? 1u : 0u;
-    MIPSF_REQUIRE(!lean_dact || (packed16 != nullptr && (arithmetic == MIPSF_PREC_F16X3 || arithmetic == MIPSF_PREC_BF16X6) && W16_EXCHANGE),
+    MIPSF_REQUIRE(!lean_dact || (packed16 != nullptr && (arithmetic == MIPSF_PREC_F16X3 || arithmetic == MIPSF_PREC_BF16X6)),
                   "the lean gradient record is read by the f16x3 / bf16x6 kernel with packed16 only");
     MIPSF_REQUIRE(packed16 == nullptr || arithmetic == MIPSF_PREC_F16X3 || arithmetic == MIPSF_PREC_BF16X6,
                   "H1 is recomputed by the f16x3 / bf16x6 arithmetic only (packed16 of the same family)");
@@ -2182,7 +1549,7 @@ extern "C" int mipsf_decoder_wgrad16(const mipsf_decoder_wgrad16_args* a, void* 
     const bool det = (flags & MIPSF_WGRAD_DETERMINISTIC) != 0u;
     const uint64_t saved_bytes = (((uint64_t)M + 127) / 128) * 4 * ACT_TILE_FLOATS * 4;
     if (live_list != nullptr) {
-        MIPSF_REQUIRE(packed16 != nullptr && (arithmetic == MIPSF_PREC_F16X3 || arithmetic == MIPSF_PREC_BF16X6) && W16_EXCHANGE && W16_TR,
+        MIPSF_REQUIRE(packed16 != nullptr && (arithmetic == MIPSF_PREC_F16X3 || arithmetic == MIPSF_PREC_BF16X6),
                       "a live-sample list is read by the transpose-read exchange form only (f16x3 / bf16x6 with packed16)");
         // (MIPSF_WGRAD_DETERMINISTIC: the list is ascending whatever the schedule and compact tiles are visited in a fixed order,
         // so nothing is put in order here; the reduce below is the ordered one)
@@ -2200,21 +1567,15 @@ extern "C" int mipsf_decoder_wgrad16(const mipsf_decoder_wgrad16_args* a, void* 
     uint32_t blocks = n_tiles < (uint32_t)cus ? n_tiles : (uint32_t)cus;
     if (blocks > (uint32_t)W16_MAX_BLOCKS) blocks = (uint32_t)W16_MAX_BLOCKS;
     const uint32_t* live = tile_live;
-#define W16(LAY, AR, RC) hipLaunchKernelGGL((decoder_wgrad16_kernel<LAY, AR, RC>), dim3(blocks), dim3(W16_BLOCK), 0, s, packed16, \
-                                            feat, x, saved, dact, dsmall, partial, M, n_tiles, live, lean_dact, live_list, (uint32_t)saved_bytes)
-#if W16_EXCHANGE && W16_TR
-#define W16C(LAY, AR) hipLaunchKernelGGL((decoder_wgrad16_kernel<LAY, AR, true, true>), dim3(blocks), dim3(W16_BLOCK), 0, s, packed16, \
-                                         feat, x, saved, dact, dsmall, partial, M, n_tiles, live, lean_dact, live_list, (uint32_t)saved_bytes)
-#else
-#define W16C(LAY, AR) ((void)0)          // (experiment builds of the other forms: the list was refused above)
-#endif
-#define W16_L(LAY) do { if (live_list) { if (arithmetic == MIPSF_PREC_F16X3) W16C(LAY, ArF16); else W16C(LAY, ArBF3); }    \
-                        else if (arithmetic == MIPSF_PREC_F16X3) { if (packed16) W16(LAY, ArF16, true); else W16(LAY, ArF16, false); } \
-                        else if (arithmetic == MIPSF_PREC_BF16X6) { if (packed16) W16(LAY, ArBF3, true); else W16(LAY, ArBF3, false); } \
-                        else W16(LAY, ArBF2, false); } while (0)
+#define W16(LAY, AR, RC, CP) hipLaunchKernelGGL((decoder_wgrad16_kernel<LAY, AR, RC, CP>), dim3(blocks), dim3(W16_BLOCK), 0, s, packed16, \
+                                                feat, x, saved, dact, dsmall, partial, M, n_tiles, live, lean_dact, live_list, (uint32_t)saved_bytes)
+    // a live-sample list: compact mode; packed16: the lean record (both the transpose-read form); else the streaming form
+#define W16_L(LAY) do { if (live_list) { if (arithmetic == MIPSF_PREC_F16X3) W16(LAY, ArF16, true, true); else W16(LAY, ArBF3, true, true); } \
+                        else if (arithmetic == MIPSF_PREC_F16X3) { if (packed16) W16(LAY, ArF16, true, false); else W16(LAY, ArF16, false, false); } \
+                        else if (arithmetic == MIPSF_PREC_BF16X6) { if (packed16) W16(LAY, ArBF3, true, false); else W16(LAY, ArBF3, false, false); } \
+                        else W16(LAY, ArBF2, false, false); } while (0)
     if (feat_layout == MIPSF_FEAT_AOS) W16_L(MIPSF_FEAT_AOS); else W16_L(MIPSF_FEAT_LEVEL_MAJOR);
 #undef W16_L
-#undef W16C
 #undef W16
     if (int e = check_launch("decoder_wgrad16")) return e;
     return wgrad_reduce_launch(partial, blocks, grads, s, det);
