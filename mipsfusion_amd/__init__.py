@@ -10,6 +10,8 @@ __version__ = "0.1.0"
 _MESH = ("marching_cubes", "extract_mesh", "extract_mesh2", "Mesh", "save_ply", "load_ply")
 _SCENE_MESH = ("SubMap", "FusedVolume", "fuse_volume", "extract_scene_mesh", "submap_from_mesh", "voxel_occupancy", "point_mask")
 _POSE_CORRECTOR = ("cloud_from_rays", "estimate_normals", "registration_icp", "switch_pose_rectifying", "IcpResult")
+_POSE_GRAPH = ("adjacent_pairs", "global_ba_gate", "build_edges", "pose_graph_enqueue", "pose_graph_optimize", "rebase",
+               "PoseGraphResult")
 
 
 def __getattr__(name):
@@ -23,4 +25,7 @@ def __getattr__(name):
     if name in _POSE_CORRECTOR:             # rectifying a switch pose by ICP (mipsfusion_amd/pose_corrector.py), the same way
         from . import pose_corrector
         return getattr(pose_corrector, name)
+    if name in _POSE_GRAPH:                 # closing a loop: the sub-map pose graph (mipsfusion_amd/pose_graph.py), the same way
+        from . import pose_graph
+        return getattr(pose_graph, name)
     raise AttributeError(f"module {__name__!r} has no attribute {name!r}")

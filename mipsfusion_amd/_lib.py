@@ -260,6 +260,20 @@ ICP_SIGNATURES = {
 }
 
 
+# include/mipsf_posegraph.h (closing a loop: Levenberg-Marquardt over the sub-maps' anchors, one launch)
+POSEGRAPH_MAX_NODES, POSEGRAPH_MAX_EDGES, POSEGRAPH_LDS_NODES, POSEGRAPH_RESULT_DOUBLES = 64, 1024, 20, 8
+POSEGRAPH_FACTORISATION_FAILED, POSEGRAPH_NAN_QUALITY, POSEGRAPH_BAD_EDGE = 1, 2, 4
+PosegraphArgs = _args("PosegraphArgs", [("n_nodes", _CU), ("n_edges", _CU), ("input_f64", _CU), ("anchors", _VP), ("edges", _VP),
+                                        ("observations", _VP), ("weights", _VP), ("steps", _CU), ("patience", _CU),
+                                        ("max_rejects", _CU), ("reserved", _CU), ("decreasing", C.c_double), ("radius", C.c_double),
+                                        ("min_diag", C.c_double), ("anchors_out", _VP), ("anchors_out32", _VP), ("result", _VP),
+                                        ("workspace", _VP)])
+POSEGRAPH_SIGNATURES = {
+    "mipsf_posegraph_workspace_bytes": (_U64, [_U32, _U32]),
+    "mipsf_posegraph_optimize": (_I, [C.POINTER(PosegraphArgs), _P]),
+}
+
+
 def buffer_size(which: int, n: int = 0, a: int = 0, b: int = 0, meta=None) -> int:
     """mipsf_buffer_size: elements of a scratch / record buffer (SIZE_* above)."""
     v = lib().mipsf_buffer_size(which, n, a, b, C.byref(meta) if meta is not None else None)
@@ -282,7 +296,7 @@ def lib() -> C.CDLL:
         handle = C.CDLL(LIB_PATH)
         for name, (res, args) in list(SIGNATURES.items()) + (list(MESH_SIGNATURES.items())
                                        + list(FUSE_SIGNATURES.items()) + list(ICP_SIGNATURES.items())
-                                       + list(COMPACT_SIGNATURES.items())):
+                                       + list(COMPACT_SIGNATURES.items()) + list(POSEGRAPH_SIGNATURES.items())):
             fn = getattr(handle, name)
             fn.restype = res
             fn.argtypes = args

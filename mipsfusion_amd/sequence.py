@@ -444,13 +444,21 @@ class GraphedSequence:
     accepted result replaces the pose the refinement starts from, and ``rectified`` records (flag, n_correspondences) per
     switch.  ``tracking.switch``'s align_threshold / including_last / min_correspondence / min_trans_dist are read with the
     reference's shipped values as defaults (0.05, 0, 2000, 0.5).  The registration restates open3d's published algorithm;
-    upstream pins no open3d version, so nothing pins this step to a recorded upstream result."""
+    upstream pins no open3d version, so nothing pins this step to a recorded upstream result.
+    ``pose_graph=True`` (opt-in; off: nothing of it is reached) closes the loop after every ("back", s) switch the way
+    InactiveMap.global_BA does: the anchors are the world poses of every sub-map's first keyframe, the adjacent pairs come from
+    the switches executed so far (each binds its keyframe to the sub-map left and the one entered, Manager.py:546,595), the key
+    edge from the frame's pose before the switch and its refined pose after it, each expressed in its sub-map's anchor; the
+    optimisation is one launch of csrc/posegraph.hip (mipsfusion_amd.pose_graph).  ``pose_graphs`` records per
+    back switch the inputs and the PoseGraphResult (None where InactiveMap.py:484-488's gate keeps the optimisation from
+    running).  The result does NOT move the runner's state: the sub-maps of this runner share one world frame and a hash grid
+    cannot be moved rigidly -- apply it with ``pose_graph.rebase`` to a trajectory or to the SubMap poses of extract_scene_mesh."""
 
     INIT_INNER = 25          # iterations per replay of the sub-map initialisation graph (500 = 20 replays)
 
     def __init__(self, cfg, dev, frames, kf_every=15, sampler="reference", first_iters=None, stream=None,
                  lookahead=None, graph_ro=True, gate_producer=True, ro_precision=None, schedule=None, decoder_precision=None,
-                 device_handover=None, deterministic=None, rectify_switch=False):
+                 device_handover=None, deterministic=None, rectify_switch=False, pose_graph=False):
         """lookahead: how many frames the sample producer runs ahead of the GPU (default: ``map_every``, one whole
         mapping period -- a BA round needs ~40 ms of serial generator work, a frame without BA ~4 ms, so the work only
         evens out over a period; the reference's own DataLoader prefetches 8 frames, mipsfusion.py:672).
@@ -461,7 +469,8 @@ class GraphedSequence:
         model's; "f16" = the opt-in plain-f16 rounds of BASELINE config 5, pose within 1e-3 of the reference's).
         deterministic: JointEncoding.deterministic of the model (default None: follow torch.are_deterministic_algorithms_enabled()
         at capture time); True = fixed-order mapping backward, the same run gives the same trajectory bit for bit.
-        rectify_switch: rectify the pose of every ("back", s) switch by ICP before its refinement (see the class docstring)."""
+        rectify_switch: rectify the pose of every ("back", s) switch by ICP before its refinement (see the class docstring).
+        pose_graph: optimise the sub-maps' pose graph after every ("back", s) switch and record it (see the class docstring)."""
         from .RandomOptimizer import RandomOptimizer
         from .graph import GraphedSteps, work_stream
         from .model import JointEncoding
@@ -472,6 +481,9 @@ class GraphedSequence:
         self.graph_ro = graph_ro and cfg["tracking"]["iter_RO"] > 0
         self.rectify_switch = bool(rectify_switch)
         self.rectified = []                                 # (flag, n_correspondences) of every rectified switch, in order
+        self.pose_graph = bool(pose_graph)
+        self.pose_graphs = []                               # inputs and result of the pose graph of every back switch, in order
+        self._bindings = []                                 # (sub-map entered, sub-map left) of every switch executed (pose_graph only)
         # device_handover (default; MIPSF_SEQ_HOST_HANDOVER=1 or False = round 4's loop): a frame's three stages hand their
         # pose over ON THE DEVICE -- RandomOptimizer state -> tracking Parameters (ops.pose_handover), tracking Parameters ->
         # the BA round's current-frame slot (a 28-byte copy) -- and the host reads ONE pose back per frame, behind the last
@@ -905,6 +917,8 @@ class GraphedSequence:
         self._store_active()
         self.model.recover_initial_param()
         self.map_opt.reset()                                # create_optimizer(): a fresh Adam
+        if self.pose_graph:
+            self._bindings.append((len(self.submaps), self.active))
         self.active = len(self.submaps)
         self.submaps[self.active] = {"kfs": [], "state": None}
         self._add_keyframe(pose)                            # first keyframe of the new sub-map: fixed[0]
@@ -921,7 +935,7 @@ class GraphedSequence:
     def _switch_back(self, target, pose, waiting):
         """active_submap_switch + local_BA_switch (mipsfusion.py:608-634, 379-444) -> the refined pose of the frame (CPU)"""
         self._store_active()
-        sm, previous = self.submaps[target], self.active
+        sm, previous, before = self.submaps[target], self.active, pose
         with torch.no_grad():
             for dst, src in zip(self._state_tensors(), sm["state"]):
                 dst.copy_(src)                              # load_state_dict of the asked sub-map, device to device
@@ -942,7 +956,29 @@ class GraphedSequence:
         self._sw_graph(n).replay()
         pose = waiting(lambda: self._get_pose(self.sw_rot, self.sw_trans, 0))
         self._add_keyframe(pose)                            # the overlapping keyframe joins the sub-map switched to
+        if self.pose_graph:
+            self._bindings.append((target, previous))
+            waiting(lambda: self._close_loop(previous, target, before, pose))
         return pose
+
+    def _close_loop(self, previous, target, before, after):
+        """InactiveMap.global_BA after a switch back: the pose graph over the sub-maps' anchors.  Recorded, not applied (see the
+        class docstring)."""
+        from . import pose_graph as pg
+        with torch.no_grad():
+            first = [self.submaps[s]["kfs"][0] for s in sorted(self.submaps)]        # not _slots_dev: that cache is the BA fill's
+            qt = self.kf_qt[torch.tensor(first, dtype=torch.int64, device=self.dev)]
+            anchors = qt_to_transform_matrix(qt[:, :4], qt[:, 4:]).detach().cpu()
+        pairs, part = pg.adjacent_pairs([list(b) for b in self._bindings])
+        X = anchors.to(torch.float64)
+        rec = {"anchors": anchors, "pairs": pairs, "id_prev": previous, "id_aft": target,
+               "local_pose_prev": torch.linalg.inv(X[previous]) @ before.detach().cpu().to(torch.float64),
+               "local_pose_after": torch.linalg.inv(X[target]) @ after.detach().cpu().to(torch.float64),
+               "key_edge_weight": float(self.cfg["mapping"].get("global_BA", {}).get("key_edge_weight", 0.1)), "result": None}
+        if pg.global_ba_gate(part, len(self.submaps)):
+            rec["result"] = pg.pose_graph_optimize(anchors, pairs, rec["local_pose_prev"], rec["local_pose_after"], previous, target,
+                                                   rec["key_edge_weight"], device=self.dev)
+        self.pose_graphs.append(rec)
 
     def _rectify(self, slots, poses, previous, pose):
         """PoseCorrector.switch_pose_rectifying in front of the switch refinement -> the pose it starts from (CPU).  The sub-maps
@@ -1253,7 +1289,7 @@ class GraphedSequence:
             self.producer.close()
         return {"frame_ms": t_frame, "ro_ms": t_ro, "go_ms": t_go, "ba_ms": t_ba, "producer_wait_ms": t_wait,
                 "est": est, "capture_ms": self.capture_ms, "detail_ms": detail, "switch": t_switch,
-                "rectified": list(self.rectified),
+                "rectified": list(self.rectified), "pose_graph": list(self.pose_graphs),
                 "submaps": {s: list(v["kfs"]) for s, v in self.submaps.items()},
                 "producer_host_ms": dict(self.producer.host_ms) if self.producer is not None else None}
 
