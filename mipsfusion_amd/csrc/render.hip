@@ -6,6 +6,7 @@
 // Reference: model/scene_rep.py:58-103 (sdf2weights, raw2outputs), :156-179 (placement), :211-236 (losses);
 // helper_functions/utils.py:21-49, 71-111 (get_masks, get_sdf_loss).
 #include "pose_dev.h"
+#include "render_dev.h"
 #include <cstring>
 #include <cstddef>
 
@@ -162,37 +163,8 @@ MIPSF_SINGLE_FP32 __global__ __launch_bounds__(RAYS_PER_BLOCK * MIPSF_WAVE) void
     place_ray(o, dv, v[6], true, noise, z_near_off, z_near_nodepth, pc, nc, z_vals, xn, counts, zs[w], sb[w], sa, n, lane);
 }
 
-// ------------------------------------------------------------------- compositing helpers
-struct RenderCfg {
-    float trunc;          // training.trunc
-    float band;           // fp32(sc_factor * trunc): z < z_min + band
-    float trunc_total;    // fp32(trunc * sc_factor): loss truncation
-    float depth_trunc;
-    int rgb_missing_nonzero;
-    float emd_w;
-};
-
-struct RayState {   // per-lane, for up to MAX_S / 64 samples per lane
-    float z_min;
-    float usum;
-};
-
-// first k in [0, S-1) with s[k] * s[k+1] < 0, else 0 (torch.argmax of an all-zero row)
-__device__ __forceinline__ uint32_t first_crossing(const float* __restrict__ srow, uint32_t S, uint32_t lane) {
-    uint32_t found = 0xFFFFFFFFu;
-    for (uint32_t base = 0; base + 1 < S; base += MIPSF_WAVE) {
-        const uint32_t k = base + lane;
-        const bool hit = (k + 1 < S) && (srow[k] * srow[k + 1] < 0.0f);
-        const unsigned long long m = __ballot(hit);
-        if (m != 0ull) {
-            found = base + (uint32_t)(__ffsll((long long)m) - 1);
-            break;
-        }
-    }
-    return found == 0xFFFFFFFFu ? 0u : found;
-}
-
 // ------------------------------------------------------------------------ forward
+// (the arithmetic of compositing, losses and their gradients: render_dev.h)
 // partial[n*8 + {0..5}] = {rgb_sq, depth_sq(valid), fs_sq, sdf_sq, fs_emd, sdf_emd}; [6] = valid flag
 struct LossFinalize {           // FUSED: the last workgroup of render_fwd_kernel finishes the losses (ticket != null)
     const uint32_t* counts;
@@ -202,9 +174,6 @@ struct LossFinalize {           // FUSED: the last workgroup of render_fwd_kerne
     float* loss_total;
     double* sums_out;           // != null: the nine sums of THIS batch are left here and the losses are NOT finished (a share of
 };                              // a ray-data-parallel batch: mipsf_render_fwd (sums); the sums of all shares go to mipsf_loss_finalize_sums)
-
-MIPSF_SINGLE_FP32 __device__ void finalize_losses(const double (&t)[9], float emd_w, uint32_t N, uint32_t S, float* __restrict__ losses,
-                                const float* __restrict__ loss_weights, float* __restrict__ loss_total);
 
 template <bool TRAIN, bool FUSED>
 __device__ __forceinline__ void render_fwd_ray(
@@ -216,27 +185,19 @@ __device__ __forceinline__ void render_fwd_ray(
     const float* rraw = raw + (size_t)n * S * 10;
     const float* rz = z_vals + (size_t)n * S;
     for (uint32_t k = lane; k < S; k += MIPSF_WAVE) srow[k] = rraw[k * 10 + 3];
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+    wave_lds_handover();
     const uint32_t kc = first_crossing(srow, S, lane);
     const float z_min = rz[kc];
     const float z_cut = z_min + rc.band;
 
     float usum = 0.f;
-    for (uint32_t k = lane; k < S; k += MIPSF_WAVE) {
-        const float q = srow[k] / rc.trunc;
-        const float u = sigmoidf_(q) * sigmoidf_(-q);
-        usum += (rz[k] < z_cut) ? u : 0.f;
-    }
+    for (uint32_t k = lane; k < S; k += MIPSF_WAVE) usum += sample_weight(srow[k], rz[k], rc.trunc, z_cut).kept();
     usum = wave_sum(usum);
     const float inv = 1.0f / (usum + 1e-8f);
 
     float a_r = 0.f, a_g = 0.f, a_b = 0.f, a_d = 0.f, a_w = 0.f;
     for (uint32_t k = lane; k < S; k += MIPSF_WAVE) {
-        const float q = srow[k] / rc.trunc;
-        const float u = (rz[k] < z_cut) ? sigmoidf_(q) * sigmoidf_(-q) : 0.f;
-        const float wn = u * inv;
+        const float wn = sample_weight(srow[k], rz[k], rc.trunc, z_cut).kept() * inv;
         if (weights_out) weights_out[(size_t)n * S + k] = wn;
         a_r += wn * sigmoidf_(rraw[k * 10 + 0]);
         a_g += wn * sigmoidf_(rraw[k * 10 + 1]);
@@ -247,65 +208,59 @@ __device__ __forceinline__ void render_fwd_ray(
     a_r = wave_sum(a_r), a_g = wave_sum(a_g), a_b = wave_sum(a_b), a_d = wave_sum(a_d), a_w = wave_sum(a_w);
     float a_v = 0.f;
     for (uint32_t k = lane; k < S; k += MIPSF_WAVE) {
-        const float q = srow[k] / rc.trunc;
-        const float u = (rz[k] < z_cut) ? sigmoidf_(q) * sigmoidf_(-q) : 0.f;
         const float t = rz[k] - a_d;
-        a_v += (u * inv) * (t * t);
+        a_v += (sample_weight(srow[k], rz[k], rc.trunc, z_cut).kept() * inv) * (t * t);
     }
     a_v = wave_sum(a_v);
-    if (lane == 0) {
-        rgb_out[3 * n] = a_r, rgb_out[3 * n + 1] = a_g, rgb_out[3 * n + 2] = a_b;
-        depth_out[n] = a_d;
-        if (var_out) var_out[n] = a_v;
-        if (disp_out) disp_out[n] = 1.0f / fmaxf(1e-10f, a_d / a_w);
-        if (acc_out) acc_out[n] = a_w;
-    }
+    if (lane == 0) store_ray_outputs(n, a_r, a_g, a_b, a_d, a_v, a_w, rgb_out, depth_out, var_out, disp_out, acc_out);
     if (!TRAIN) return;
 
     const float d = target_d[n];
-    const bool valid = (d > 0.f) && (d < rc.depth_trunc);
-    const float cw = (valid || rc.rgb_missing_nonzero) ? 1.f : 0.f;
-    float p_fs = 0.f, p_sd = 0.f, p_fe = 0.f, p_se = 0.f;
-    const float T = rc.trunc_total;
-    const bool has_depth = d > 0.f;
-    for (uint32_t k = lane; k < S; k += MIPSF_WAVE) {
-        const float z = rz[k], s = srow[k];
-        const bool front = z < d - T;
-        const bool back = z > d + T;
-        const float fm = front ? 1.f : 0.f;
-        const float bm = (!front && !back && has_depth) ? 1.f : 0.f;
-        const float ef = s * fm - fm;
-        p_fs += ef * ef;
-        const float es = (z + s * T) * bm - d * bm;
-        p_sd += es * es;
-        if (rc.emd_w > 0.f) {
-            const float gt = (((d - z) + T) / (2.f * T)) * 4.f;
-            float fe = 0.f, se = 0.f;
+    float p[4] = {0.f, 0.f, 0.f, 0.f};
+    for (uint32_t k = lane; k < S; k += MIPSF_WAVE) loss_terms_add(rz[k], srow[k], d, rc.trunc_total, rc.emd_w, rraw + k * 10 + 5, p);
 #pragma unroll
-            for (int c = 0; c < 5; ++c) {
-                const float p = rraw[k * 10 + 5 + c];
-                fe += p * (float)(4 - c) * fm;
-                se += fabsf(gt - (float)c) * bm * p;
-            }
-            p_fe += fe;
-            p_se += se;
-        }
+    for (int j = 0; j < 4; ++j) p[j] = wave_sum(p[j]);
+    loss_row(a_r, a_g, a_b, a_d, target_rgb[3 * n], target_rgb[3 * n + 1], target_rgb[3 * n + 2], d, rc, p, row);
+    if (!FUSED && lane == 0) {       // (FUSED: the row stays in registers; every value is wave-uniform after the reductions above)
+        float* out = partial + (size_t)n * 8;
+#pragma unroll
+        for (int j = 0; j < 7; ++j) out[j] = row[j];
+        out[7] = 0.f;
     }
-    p_fs = wave_sum(p_fs), p_sd = wave_sum(p_sd), p_fe = wave_sum(p_fe), p_se = wave_sum(p_se);
-    float* p = partial + (size_t)n * 8;
-    const float e0 = a_r * cw - target_rgb[3 * n] * cw;
-    const float e1 = a_g * cw - target_rgb[3 * n + 1] * cw;
-    const float e2 = a_b * cw - target_rgb[3 * n + 2] * cw;
-    const float ed = a_d - d;
-    const float v0 = e0 * e0 + e1 * e1 + e2 * e2, v1 = valid ? ed * ed : 0.f, v6 = valid ? 1.f : 0.f;
-    if (!FUSED) {
-        if (lane == 0) {
-            p[0] = v0, p[1] = v1;
-            p[2] = p_fs, p[3] = p_sd, p[4] = p_fe, p[5] = p_se;
-            p[6] = v6, p[7] = 0.f;
-        }
-    } else {        // (every value is wave-uniform after the reductions above)
-        row[0] = v0, row[1] = v1, row[2] = p_fs, row[3] = p_sd, row[4] = p_fe, row[5] = p_se, row[6] = v6;
+}
+
+// losses[8] = {rgb_loss, depth_loss, sdf_loss, fs_loss, psnr, fs_weight, sdf_weight, n_valid} from the batch's nine sums
+// t = {the six of `partial`, n_valid, n_front, n_band}
+MIPSF_SINGLE_FP32 __device__ void finalize_losses(const double (&t)[9], float emd_w, uint32_t N, uint32_t S, float* __restrict__ losses,
+                                const float* __restrict__ loss_weights, float* __restrict__ loss_total) {
+    const double NS = (double)N * (double)S;
+    float fs_w, sdf_w;
+    band_weights((float)t[7], (float)t[8], fs_w, sdf_w);
+    const float rgb_loss = (float)(t[0] / (3.0 * (double)N));
+    const float depth_loss = (float)(t[1] / t[6]);   // no valid depth -> 0/0 = NaN (mse of an empty tensor)
+    float fs = (float)(t[2] / NS) * fs_w;
+    float sd = (float)(t[3] / NS) * sdf_w;
+    if (emd_w > 0.f) {
+        fs = fs + ((float)(t[4] / NS) / 250.f) * emd_w;
+        sd = sd + ((float)(t[5] / NS) / 5000.f) * emd_w;
+    }
+    losses[0] = rgb_loss;
+    losses[1] = depth_loss;
+    losses[2] = sd;
+    losses[3] = fs;
+    losses[4] = -10.f * logf(rgb_loss) / logf(10.f);
+    losses[5] = fs_w;
+    losses[6] = sdf_w;
+    losses[7] = (float)t[6];
+    // the training objective itself (MIPSFusion.get_loss_from_ret, mipsfusion.py:142-152): the same products added left
+    // to right in fp32 -- saves the caller a dot product forward and a scaling pass backward (5 us launches each)
+    if (loss_total) {
+        float tot = 0.0f;
+        tot = tot + loss_weights[0] * rgb_loss;
+        tot = tot + loss_weights[1] * depth_loss;
+        tot = tot + loss_weights[2] * sd;
+        tot = tot + loss_weights[3] * fs;
+        loss_total[0] = tot;
     }
 }
 
@@ -412,10 +367,10 @@ MIPSF_SINGLE_FP32 __global__ __launch_bounds__(RPB * MIPSF_WAVE) void render_fwd
 // The one-launch training forward again, for S <= 128, with the ray's data read ONCE: its row of `raw` (S x 10 floats, contiguous)
 // is staged in LDS by coalesced loads -- render_fwd_ray / render_bwd_kernel read it component by component, 40 bytes from lane
 // to lane, in every one of their passes, and fetch z[first crossing] from memory behind the ballot -- its depths sit in registers
-// (two samples per lane), every sigmoid is evaluated once.  Same expressions in the same order: the same bits as
-// render_fwd_kernel<true, true, 16>.
+// (two samples per lane), every sigmoid is evaluated once.  The arithmetic is render_dev.h's, called in the same order: the same
+// bits as render_fwd_kernel<true, true, 16>.
 // DRAW: d objective / d raw for an objective gradient of exactly 1 (g_total = 1, no other gradient: what `loss.backward()` on
-// render_fwd's loss_total means) is written as well -- render_bwd_kernel's expressions, bit for bit.  What that kernel takes
+// render_fwd's loss_total means) is written as well -- the same bits as render_bwd_kernel's, by the same functions.  What that kernel takes
 // from the finished losses (fs_weight, sdf_weight, n_valid) depends on the sample depths and the target depths only: every
 // workgroup adds the per-ray counts of ALL rays itself (integers: exact in any order; 48 KB from L2, under the staging loads).
 constexpr int RT_RPB = 16;          // rays per workgroup (the ticket traffic: see render_fwd_kernel)
@@ -467,7 +422,7 @@ MIPSF_SINGLE_FP32 __global__ __launch_bounds__(RT_RPB * MIPSF_WAVE) void render_
             for (int u = 0; u < 4; ++u) {
                 if (m0 + (uint32_t)u * T >= N) break;
                 cf += c[u].x, cb += c[u].y;
-                cv += ((dd[u] > 0.f) && (dd[u] < rc.depth_trunc)) ? 1u : 0u;
+                cv += depth_valid(dd[u], rc.depth_trunc) ? 1u : 0u;
             }
         }
     }
@@ -502,27 +457,16 @@ MIPSF_SINGLE_FP32 __global__ __launch_bounds__(RT_RPB * MIPSF_WAVE) void render_
 #pragma unroll
         for (int q = 0; q < RT_RPB; ++q) n_front += cred[q][0], n_band += cred[q][1], n_valid += cred[q][2];
     } else {
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-        __builtin_amdgcn_wave_barrier();
-        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+        wave_lds_handover();
     }
 
     float row[7] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
     if (live) {
-        float sv[RT_KMAX], u_[RT_KMAX], sg[RT_KMAX], c0[RT_KMAX], c1[RT_KMAX], c2[RT_KMAX];
-        bool keep[RT_KMAX];
-        // first k in [0, S - 1) with s[k] * s[k + 1] < 0, else 0 (first_crossing)
-        uint32_t kc = 0;
-        bool found = false;
+        float sv[RT_KMAX], c0[RT_KMAX], c1[RT_KMAX], c2[RT_KMAX];
+        SampleWeight sw[RT_KMAX];
 #pragma unroll
-        for (int j = 0; j < RT_KMAX; ++j) {
-            const uint32_t k = lane + (uint32_t)j * MIPSF_WAVE;
-            sv[j] = in[j] ? sraw[k * 10 + 3] : 0.0f;
-            const float nxt = (k + 1 < S) ? sraw[(k + 1) * 10 + 3] : 0.0f;
-            const bool hit = (k + 1 < S) && (sv[j] * nxt < 0.0f);
-            const unsigned long long m = __ballot(hit);
-            if (!found && m != 0ull) kc = (uint32_t)j * MIPSF_WAVE + (uint32_t)(__ffsll((long long)m) - 1), found = true;
-        }
+        for (int j = 0; j < RT_KMAX; ++j) sv[j] = in[j] ? sraw[(lane + (uint32_t)j * MIPSF_WAVE) * 10 + 3] : 0.0f;
+        const uint32_t kc = first_crossing_staged<RT_KMAX>(sraw, sv, S, lane);
         float zsel = zz[0];
 #pragma unroll
         for (int j = 1; j < RT_KMAX; ++j) zsel = (kc / MIPSF_WAVE == (uint32_t)j) ? zz[j] : zsel;
@@ -533,11 +477,8 @@ MIPSF_SINGLE_FP32 __global__ __launch_bounds__(RT_RPB * MIPSF_WAVE) void render_
 #pragma unroll
         for (int j = 0; j < RT_KMAX; ++j) {
             if (!in[j]) continue;
-            const float q = sv[j] / rc.trunc;
-            sg[j] = sigmoidf_(q);
-            u_[j] = sg[j] * sigmoidf_(-q);
-            keep[j] = zz[j] < z_cut;
-            usum += keep[j] ? u_[j] : 0.f;
+            sw[j] = sample_weight(sv[j], zz[j], rc.trunc, z_cut);
+            usum += sw[j].kept();
         }
         usum = wave_sum(usum);
         const float inv = 1.0f / (usum + 1e-8f);
@@ -547,8 +488,7 @@ MIPSF_SINGLE_FP32 __global__ __launch_bounds__(RT_RPB * MIPSF_WAVE) void render_
         for (int j = 0; j < RT_KMAX; ++j) {
             if (!in[j]) continue;
             const uint32_t k = lane + (uint32_t)j * MIPSF_WAVE;
-            const float u = keep[j] ? u_[j] : 0.f;
-            const float wn = u * inv;
+            const float wn = sw[j].kept() * inv;
             if (weights_out) weights_out[(size_t)n * S + k] = wn;
             c0[j] = sigmoidf_(sraw[k * 10 + 0]), c1[j] = sigmoidf_(sraw[k * 10 + 1]), c2[j] = sigmoidf_(sraw[k * 10 + 2]);
             a_r += wn * c0[j];
@@ -562,118 +502,47 @@ MIPSF_SINGLE_FP32 __global__ __launch_bounds__(RT_RPB * MIPSF_WAVE) void render_
 #pragma unroll
         for (int j = 0; j < RT_KMAX; ++j) {
             if (!in[j]) continue;
-            const float u = keep[j] ? u_[j] : 0.f;
             const float t = zz[j] - a_d;
-            a_v += (u * inv) * (t * t);
+            a_v += (sw[j].kept() * inv) * (t * t);
         }
         a_v = wave_sum(a_v);
-        if (lane == 0) {
-            rgb_out[3 * n] = a_r, rgb_out[3 * n + 1] = a_g, rgb_out[3 * n + 2] = a_b;
-            depth_out[n] = a_d;
-            if (var_out) var_out[n] = a_v;
-            if (disp_out) disp_out[n] = 1.0f / fmaxf(1e-10f, a_d / a_w);
-            if (acc_out) acc_out[n] = a_w;
-        }
+        if (lane == 0) store_ray_outputs(n, a_r, a_g, a_b, a_d, a_v, a_w, rgb_out, depth_out, var_out, disp_out, acc_out);
 
-        // ---- the losses' per-ray sums (render_fwd_ray)
-        const bool valid = (d > 0.f) && (d < rc.depth_trunc);
-        const float cw = (valid || rc.rgb_missing_nonzero) ? 1.f : 0.f;
-        float p_fs = 0.f, p_sd = 0.f, p_fe = 0.f, p_se = 0.f;
-        const float TT = rc.trunc_total;
-        const bool has_depth = d > 0.f;
+        // ---- the losses' per-ray sums
+        float p[4] = {0.f, 0.f, 0.f, 0.f};
 #pragma unroll
         for (int j = 0; j < RT_KMAX; ++j) {
             if (!in[j]) continue;
-            const uint32_t k = lane + (uint32_t)j * MIPSF_WAVE;
-            const float z = zz[j], s = sv[j];
-            const bool front = z < d - TT;
-            const bool back = z > d + TT;
-            const float fm = front ? 1.f : 0.f;
-            const float bm = (!front && !back && has_depth) ? 1.f : 0.f;
-            const float ef = s * fm - fm;
-            p_fs += ef * ef;
-            const float es = (z + s * TT) * bm - d * bm;
-            p_sd += es * es;
-            if (rc.emd_w > 0.f) {
-                const float gt = (((d - z) + TT) / (2.f * TT)) * 4.f;
-                float fe = 0.f, se = 0.f;
-#pragma unroll
-                for (int c = 0; c < 5; ++c) {
-                    const float p = sraw[k * 10 + 5 + c];
-                    fe += p * (float)(4 - c) * fm;
-                    se += fabsf(gt - (float)c) * bm * p;
-                }
-                p_fe += fe;
-                p_se += se;
-            }
+            loss_terms_add(zz[j], sv[j], d, rc.trunc_total, rc.emd_w, sraw + (lane + (uint32_t)j * MIPSF_WAVE) * 10 + 5, p);
         }
-        p_fs = wave_sum(p_fs), p_sd = wave_sum(p_sd), p_fe = wave_sum(p_fe), p_se = wave_sum(p_se);
-        const float e0 = a_r * cw - t_r * cw;
-        const float e1 = a_g * cw - t_g * cw;
-        const float e2 = a_b * cw - t_b * cw;
-        const float ed = a_d - d;
-        row[0] = e0 * e0 + e1 * e1 + e2 * e2, row[1] = valid ? ed * ed : 0.f, row[2] = p_fs, row[3] = p_sd, row[4] = p_fe, row[5] = p_se;
-        row[6] = valid ? 1.f : 0.f;
+#pragma unroll
+        for (int j = 0; j < 4; ++j) p[j] = wave_sum(p[j]);
+        loss_row(a_r, a_g, a_b, a_d, t_r, t_g, t_b, d, rc, p, row);
 
         if (DRAW) {
-            // ---- render_bwd_kernel with g_losses = g_rgb = g_depth = null, g_total = 1, N_norm = N
+            // ---- what render_bwd_kernel writes for g_losses = g_rgb = g_depth = null, g_total = 1, N_norm = N
             float gl[4];
 #pragma unroll
-            for (int k = 0; k < 4; ++k) gl[k] = 0.f + 1.0f * fin.loss_weights[k];
-            const float gR = gl[0], gD = gl[1], gS = gl[2], gF = gl[3];
-            const float nf = (float)n_front, nb = (float)n_band;
-            const float total = nf + nb;
-            const float fs_w = 1.0f - nf / total, sdf_w = 1.0f - nb / total;      // finalize_losses
-            const float NS = (float)N * (float)S;
-            float G_r = 0.f, G_g = 0.f, G_b = 0.f, G_d = 0.f;
-            const float k_rgb = gR * 2.f * cw * cw / (3.f * (float)N);
-            G_r += k_rgb * (a_r - t_r);
-            G_g += k_rgb * (a_g - t_g);
-            G_b += k_rgb * (a_b - t_b);
-            if (valid) G_d += gD * 2.f * (a_d - d) / (float)n_valid;
+            for (int k = 0; k < 4; ++k) gl[k] = loss_grad(0.f, 1.0f, fin.loss_weights[k]);
+            LossGrad lg = {gl[3], gl[2], 0.f, 0.f, (float)N * (float)S};
+            band_weights((float)n_front, (float)n_band, lg.fs_w, lg.sdf_w);
+            MapGrad G = {0.f, 0.f, 0.f, 0.f};
+            map_grad_add(G, gl[0], gl[1], a_r, a_g, a_b, a_d, t_r, t_g, t_b, d, rc, (float)N, (float)n_valid);
             float dot = 0.f;
 #pragma unroll
             for (int j = 0; j < RT_KMAX; ++j) {
                 if (!in[j]) continue;
-                const float wn = (keep[j] ? u_[j] : 0.f) * inv;
-                const float Gk = G_r * c0[j] + G_g * c1[j] + G_b * c2[j] + G_d * zz[j];
-                dot += Gk * wn;
+                dot += G.at(c0[j], c1[j], c2[j], zz[j]) * (sw[j].kept() * inv);
             }
             dot = wave_sum(dot);
 #pragma unroll
             for (int j = 0; j < RT_KMAX; ++j) {
                 if (!in[j]) continue;
-                const uint32_t k = lane + (uint32_t)j * MIPSF_WAVE;
-                const float z = zz[j], s = sv[j];
-                const float a = u_[j];
-                const float wn = (keep[j] ? a : 0.f) * inv;
-                const float Gk = G_r * c0[j] + G_g * c1[j] + G_b * c2[j] + G_d * z;
-                float ds = keep[j] ? (Gk - dot) * inv * (a * (1.f - 2.f * sg[j]) / rc.trunc) : 0.f;
-                float dp[5] = {0.f, 0.f, 0.f, 0.f, 0.f};
-                const bool front = z < d - TT;
-                const bool back = z > d + TT;
-                const float fm = front ? 1.f : 0.f;
-                const float bm = (!front && !back && has_depth) ? 1.f : 0.f;
-                ds += gF * fs_w * (2.f / NS) * fm * (s * fm - fm);
-                ds += gS * sdf_w * (2.f / NS) * (bm * TT) * ((z + s * TT) * bm - d * bm);
-                if (rc.emd_w > 0.f) {
-                    const float gt = (((d - z) + TT) / (2.f * TT)) * 4.f;
-                    const float kf = gF * rc.emd_w / (250.f * NS), ks = gS * rc.emd_w / (5000.f * NS);
-#pragma unroll
-                    for (int c = 0; c < 5; ++c) dp[c] = kf * fm * (float)(4 - c) + ks * bm * fabsf(gt - (float)c);
-                }
-                float* o = sraw + k * 10;          // this sample's own words: nobody else reads them any more
-                o[0] = G_r * wn * c0[j] * (1.f - c0[j]);
-                o[1] = G_g * wn * c1[j] * (1.f - c1[j]);
-                o[2] = G_b * wn * c2[j] * (1.f - c2[j]);
-                o[3] = ds;
-                o[4] = 0.f;
-#pragma unroll
-                for (int c = 0; c < 5; ++c) o[5 + c] = dp[c];
+                // (into the sample's own words of the staged row: nobody else reads them any more)
+                sample_grad_record(sraw + (lane + (uint32_t)j * MIPSF_WAVE) * 10, G, dot, inv, sw[j], c0[j], c1[j], c2[j], zz[j], sv[j], d,
+                                   rc, true, lg);
             }
-            __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-            __builtin_amdgcn_wave_barrier();
-            __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+            wave_lds_handover();
             float* rdr = draw + (size_t)n * row_words;
 #pragma unroll
             for (int q = 0; q < RT_KMAX * 10; ++q) {
@@ -685,7 +554,7 @@ MIPSF_SINGLE_FP32 __global__ __launch_bounds__(RT_RPB * MIPSF_WAVE) void render_
     render_fused_tail<RT_RPB>(row, n, w, lane, N, S, rc, partial, fin);
 }
 
-// losses[8] = {rgb_loss, depth_loss, sdf_loss, fs_loss, psnr, fs_weight, sdf_weight, n_valid}
+// the second launch of the two-launch form: the rays' rows of `partial` and their counts, added in fp64, to finalize_losses
 constexpr int LF_BLOCK = 1024;
 __global__ __launch_bounds__(LF_BLOCK) void loss_finalize_kernel(const float* __restrict__ partial,
                                                             const uint32_t* __restrict__ counts, float emd_w,
@@ -733,41 +602,6 @@ __global__ __launch_bounds__(LF_BLOCK) void loss_finalize_kernel(const float* __
     if (lane == 0) finalize_losses(t, emd_w, N, S, losses, loss_weights, loss_total);
 }
 
-MIPSF_SINGLE_FP32 __device__ void finalize_losses(const double (&t)[9], float emd_w, uint32_t N, uint32_t S, float* __restrict__ losses,
-                                const float* __restrict__ loss_weights, float* __restrict__ loss_total) {
-    const double NS = (double)N * (double)S;
-    const float n_front = (float)t[7], n_band = (float)t[8];
-    const float total = n_front + n_band;
-    const float fs_w = 1.0f - n_front / total;     // 0/0 -> NaN exactly like the reference
-    const float sdf_w = 1.0f - n_band / total;
-    const float rgb_loss = (float)(t[0] / (3.0 * (double)N));
-    const float depth_loss = (float)(t[1] / t[6]);   // no valid depth -> 0/0 = NaN (mse of an empty tensor)
-    float fs = (float)(t[2] / NS) * fs_w;
-    float sd = (float)(t[3] / NS) * sdf_w;
-    if (emd_w > 0.f) {
-        fs = fs + ((float)(t[4] / NS) / 250.f) * emd_w;
-        sd = sd + ((float)(t[5] / NS) / 5000.f) * emd_w;
-    }
-    losses[0] = rgb_loss;
-    losses[1] = depth_loss;
-    losses[2] = sd;
-    losses[3] = fs;
-    losses[4] = -10.f * logf(rgb_loss) / logf(10.f);
-    losses[5] = fs_w;
-    losses[6] = sdf_w;
-    losses[7] = (float)t[6];
-    // the training objective itself (MIPSFusion.get_loss_from_ret, mipsfusion.py:142-152): the same products added left
-    // to right in fp32 -- saves the caller a dot product forward and a scaling pass backward (5 us launches each)
-    if (loss_total) {
-        float tot = 0.0f;
-        tot = tot + loss_weights[0] * rgb_loss;
-        tot = tot + loss_weights[1] * depth_loss;
-        tot = tot + loss_weights[2] * sd;
-        tot = tot + loss_weights[3] * fs;
-        loss_total[0] = tot;
-    }
-}
-
 // the losses of a batch whose nine sums were formed elsewhere (the all-reduced sums of a ray-data-parallel batch's shares)
 MIPSF_SINGLE_FP32 __global__ void loss_finalize_sums_kernel(const double* __restrict__ sums, float emd_w, uint32_t N, uint32_t S,
                                           float* __restrict__ losses, const float* __restrict__ loss_weights,
@@ -798,24 +632,18 @@ MIPSF_SINGLE_FP32 __global__ __launch_bounds__(RAYS_PER_BLOCK * MIPSF_WAVE) void
     float* rdr = draw + (size_t)n * S * 10;
     float* srow = ssdf[w];
     for (uint32_t k = lane; k < S; k += MIPSF_WAVE) srow[k] = rraw[k * 10 + 3];
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+    wave_lds_handover();
     const uint32_t kc = first_crossing(srow, S, lane);
     const float z_cut = rz[kc] + rc.band;
 
     // recompute the forward reductions
     float usum = 0.f;
-    for (uint32_t k = lane; k < S; k += MIPSF_WAVE) {
-        const float q = srow[k] / rc.trunc;
-        usum += (rz[k] < z_cut) ? sigmoidf_(q) * sigmoidf_(-q) : 0.f;
-    }
+    for (uint32_t k = lane; k < S; k += MIPSF_WAVE) usum += sample_weight(srow[k], rz[k], rc.trunc, z_cut).kept();
     usum = wave_sum(usum);
     const float inv = 1.0f / (usum + 1e-8f);
     float a_r = 0.f, a_g = 0.f, a_b = 0.f, a_d = 0.f;
     for (uint32_t k = lane; k < S; k += MIPSF_WAVE) {
-        const float q = srow[k] / rc.trunc;
-        const float wn = ((rz[k] < z_cut) ? sigmoidf_(q) * sigmoidf_(-q) : 0.f) * inv;
+        const float wn = sample_weight(srow[k], rz[k], rc.trunc, z_cut).kept() * inv;
         a_r += wn * sigmoidf_(rraw[k * 10 + 0]);
         a_g += wn * sigmoidf_(rraw[k * 10 + 1]);
         a_b += wn * sigmoidf_(rraw[k * 10 + 2]);
@@ -823,74 +651,34 @@ MIPSF_SINGLE_FP32 __global__ __launch_bounds__(RAYS_PER_BLOCK * MIPSF_WAVE) void
     }
     a_r = wave_sum(a_r), a_g = wave_sum(a_g), a_b = wave_sum(a_b), a_d = wave_sum(a_d);
 
-    // gradients reaching the rendered maps
-    float G_r = g_rgb ? g_rgb[3 * n] : 0.f, G_g = g_rgb ? g_rgb[3 * n + 1] : 0.f, G_b = g_rgb ? g_rgb[3 * n + 2] : 0.f;
-    float G_d = g_depth ? g_depth[n] : 0.f;
-    float d = 0.f, gS = 0.f, gF = 0.f, fs_w = 0.f, sdf_w = 0.f;
-    const float NS = (float)N_norm * (float)S;
+    // gradients reaching the rendered maps: given directly, and through the losses (the weights and the valid count are
+    // taken from the finished losses)
+    MapGrad G = {g_rgb ? g_rgb[3 * n] : 0.f, g_rgb ? g_rgb[3 * n + 1] : 0.f, g_rgb ? g_rgb[3 * n + 2] : 0.f, g_depth ? g_depth[n] : 0.f};
+    float d = 0.f;
+    LossGrad lg = {0.f, 0.f, 0.f, 0.f, (float)N_norm * (float)S};
     if (train) {
         d = target_d[n];
-        const bool valid = (d > 0.f) && (d < rc.depth_trunc);
-        const float cw = (valid || rc.rgb_missing_nonzero) ? 1.f : 0.f;
-        // d objective / d {rgb, depth, sdf, fs}_loss: given directly and / or as (d objective / d total) x weights
         float gl[4];
 #pragma unroll
-        for (int k = 0; k < 4; ++k) gl[k] = (g_losses ? g_losses[k] : 0.f) + (g_total ? g_total[0] * loss_weights[k] : 0.f);
-        const float gR = gl[0], gD = gl[1];
-        gS = gl[2], gF = gl[3];
-        fs_w = losses[5], sdf_w = losses[6];
-        const float k_rgb = gR * 2.f * cw * cw / (3.f * (float)N_norm);
-        G_r += k_rgb * (a_r - target_rgb[3 * n]);
-        G_g += k_rgb * (a_g - target_rgb[3 * n + 1]);
-        G_b += k_rgb * (a_b - target_rgb[3 * n + 2]);
-        if (valid) G_d += gD * 2.f * (a_d - d) / losses[7];
+        for (int k = 0; k < 4; ++k)
+            gl[k] = loss_grad(g_losses ? g_losses[k] : 0.f, g_total ? g_total[0] : 0.f, g_total ? loss_weights[k] : 0.f);
+        lg.gS = gl[2], lg.gF = gl[3];
+        lg.fs_w = losses[5], lg.sdf_w = losses[6];
+        map_grad_add(G, gl[0], gl[1], a_r, a_g, a_b, a_d, target_rgb[3 * n], target_rgb[3 * n + 1], target_rgb[3 * n + 2], d, rc,
+                     (float)N_norm, losses[7]);
     }
     // dot = sum_k G_k * wn_k
     float dot = 0.f;
     for (uint32_t k = lane; k < S; k += MIPSF_WAVE) {
-        const float q = srow[k] / rc.trunc;
-        const float wn = ((rz[k] < z_cut) ? sigmoidf_(q) * sigmoidf_(-q) : 0.f) * inv;
-        const float Gk = G_r * sigmoidf_(rraw[k * 10 + 0]) + G_g * sigmoidf_(rraw[k * 10 + 1]) +
-                         G_b * sigmoidf_(rraw[k * 10 + 2]) + G_d * rz[k];
-        dot += Gk * wn;
+        const float wn = sample_weight(srow[k], rz[k], rc.trunc, z_cut).kept() * inv;
+        dot += G.at(sigmoidf_(rraw[k * 10 + 0]), sigmoidf_(rraw[k * 10 + 1]), sigmoidf_(rraw[k * 10 + 2]), rz[k]) * wn;
     }
     dot = wave_sum(dot);
 
-    const float T = rc.trunc_total;
-    const bool has_depth = d > 0.f;
     for (uint32_t k = lane; k < S; k += MIPSF_WAVE) {
         const float z = rz[k], s = srow[k];
-        const float q = s / rc.trunc;
-        const float sg = sigmoidf_(q);
-        const bool keep = z < z_cut;
-        const float a = sg * sigmoidf_(-q);
-        const float wn = (keep ? a : 0.f) * inv;
         const float c0 = sigmoidf_(rraw[k * 10 + 0]), c1 = sigmoidf_(rraw[k * 10 + 1]), c2 = sigmoidf_(rraw[k * 10 + 2]);
-        const float Gk = G_r * c0 + G_g * c1 + G_b * c2 + G_d * z;
-        float ds = keep ? (Gk - dot) * inv * (a * (1.f - 2.f * sg) / rc.trunc) : 0.f;
-        float dp[5] = {0.f, 0.f, 0.f, 0.f, 0.f};
-        if (train) {
-            const bool front = z < d - T;
-            const bool back = z > d + T;
-            const float fm = front ? 1.f : 0.f;
-            const float bm = (!front && !back && has_depth) ? 1.f : 0.f;
-            ds += gF * fs_w * (2.f / NS) * fm * (s * fm - fm);
-            ds += gS * sdf_w * (2.f / NS) * (bm * T) * ((z + s * T) * bm - d * bm);
-            if (rc.emd_w > 0.f) {
-                const float gt = (((d - z) + T) / (2.f * T)) * 4.f;
-                const float kf = gF * rc.emd_w / (250.f * NS), ks = gS * rc.emd_w / (5000.f * NS);
-#pragma unroll
-                for (int c = 0; c < 5; ++c) dp[c] = kf * fm * (float)(4 - c) + ks * bm * fabsf(gt - (float)c);
-            }
-        }
-        float* o = rdr + k * 10;
-        o[0] = G_r * wn * c0 * (1.f - c0);
-        o[1] = G_g * wn * c1 * (1.f - c1);
-        o[2] = G_b * wn * c2 * (1.f - c2);
-        o[3] = ds;
-        o[4] = 0.f;
-#pragma unroll
-        for (int c = 0; c < 5; ++c) o[5 + c] = dp[c];
+        sample_grad_record(rdr + k * 10, G, dot, inv, sample_weight(s, z, rc.trunc, z_cut), c0, c1, c2, z, s, d, rc, train != 0, lg);
     }
 }
 
@@ -1081,127 +869,106 @@ int mipsf_place_pose_bwd(const float* dxn, const float* z_vals, const mipsf_rend
     return check_launch("place_pose_bwd");
 }
 
-// render_train_kernel (S <= RT_MAX_S): RT_RPB x S x 40 bytes of dynamic LDS beside ~9.5 KB of static LDS (together above 64 KB
-// from S = 88, 90 KB at S = 128: inside gfx950's 160 KB).  Returns -1 -- nothing launched -- when the device does not grant the
-// dynamic size (a build for another ARCH): the caller then takes the kernel without the LDS row.
-static int launch_render_train(const float* raw, const float* z_vals, const float* target_rgb, const float* target_d,
-                               const RenderCfg& rc, float* rgb, float* depth, float* depth_var, float* disp, float* acc,
-                               float* weights, float* partial, uint32_t N, uint32_t S, const LossFinalize& fin, float* draw,
-                               hipStream_t s) {
-    const uint32_t lds = (uint32_t)RT_RPB * S * 40u;
-    const int two = S > MIPSF_WAVE ? 1 : 0;       // samples per lane - 1
-    const void* fn[2][2] = {{(const void*)render_train_kernel<false, 1>, (const void*)render_train_kernel<false, 2>},
-                            {(const void*)render_train_kernel<true, 1>, (const void*)render_train_kernel<true, 2>}};
-    static uint32_t attr_dev[MAX_DEVICES][2] = {};
-    uint32_t& attr = attr_dev[device_slot()][draw ? 1 : 0];
-    if (lds > 48u * 1024u && lds > attr) {        // (only the two-samples-per-lane kernels get there)
-        if (hipFuncSetAttribute(fn[draw ? 1 : 0][1], hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess) {
-            (void)hipGetLastError();
-            return -1;
-        }
-        attr = lds;       // (two threads racing here both set the attribute to a size that covers their launch: benign)
-    }
-    const dim3 grid((N + RT_RPB - 1) / RT_RPB), block(RT_RPB * MIPSF_WAVE);
-#define RT_LAUNCH(D, K)                                                                                                         \
-    hipLaunchKernelGGL((render_train_kernel<D, K>), grid, block, lds, s, raw, z_vals, target_rgb, target_d, rc, rgb, depth, depth_var, \
-                       disp, acc, weights, partial, N, S, fin, draw)
-    if (draw) { if (two) RT_LAUNCH(true, 2); else RT_LAUNCH(true, 1); }
-    else { if (two) RT_LAUNCH(false, 2); else RT_LAUNCH(false, 1); }
-#undef RT_LAUNCH
+}  // extern "C"
+
+// The two render argument blocks are also taken in the first form of this ABI version, which ends before the block's last
+// field (short_size = that field's offset): the field then reads as zero.  Any other struct_size is refused.
+template <typename A>
+static int read_args(A* a, const A* in, size_t short_size, const char* name) {
+    MIPSF_REQUIRE(in != nullptr, "null argument block");
+    MIPSF_REQUIRE(in->struct_size == sizeof(A) || in->struct_size == short_size, "%s: struct_size %u, this library expects %u", name,
+                  in->struct_size, (unsigned)sizeof(A));
+    *a = A{};
+    memcpy(a, in, in->struct_size);
     return 0;
 }
 
-static int render_fwd_sums(const float* raw, const float* z_vals, const float* target_rgb, const float* target_d,
-                           const uint32_t* counts, const mipsf_render_cfg* cfg, float* rgb, float* depth, float* depth_var,
-                           float* disp, float* acc, float* weights, float* partial, double* sums, uint32_t* ticket, uint32_t N,
-                           uint32_t S, void* stream);
+// The training forward in ONE launch (ticket): render_train_kernel -- the ray read once; with a->draw also the backward of the
+// objective -- when S <= RT_MAX_S and the device grants its RT_RPB x S x 40 bytes of dynamic LDS (beside ~9.5 KB of static LDS:
+// together above 64 KB from S = 88, 90 KB at S = 128, inside gfx950's 160 KB; a build for another ARCH may not), else
+// render_fwd_kernel<true, true, 16>.  fin says what the last workgroup does with the batch's nine sums.
+static int launch_render_ticket(const mipsf_render_fwd_args* a, const RenderCfg& rc, const LossFinalize& fin, const char* what,
+                                hipStream_t s) {
+    const uint32_t N = a->N, S = a->S;
+    const dim3 grid((N + RT_RPB - 1) / RT_RPB), block(RT_RPB * MIPSF_WAVE);
+    bool granted = S <= RT_MAX_S;
+    if (granted) {
+        const uint32_t lds = (uint32_t)RT_RPB * S * 40u;
+        const int two = S > MIPSF_WAVE ? 1 : 0;       // samples per lane - 1
+        static uint32_t attr_dev[MAX_DEVICES][2] = {};
+        uint32_t& attr = attr_dev[device_slot()][a->draw ? 1 : 0];
+        if (lds > 48u * 1024u && lds > attr) {        // (only the two-samples-per-lane kernels get there)
+            const void* fn = a->draw ? (const void*)render_train_kernel<true, 2> : (const void*)render_train_kernel<false, 2>;
+            granted = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) == hipSuccess;
+            if (granted) attr = lds;       // (two threads racing here both set the attribute to a size that covers their launch: benign)
+            else (void)hipGetLastError();
+        }
+        if (granted) {
+#define RT_LAUNCH(D, K)                                                                                                              \
+    hipLaunchKernelGGL((render_train_kernel<D, K>), grid, block, lds, s, a->raw, a->z_vals, a->target_rgb, a->target_d, rc, a->rgb, \
+                       a->depth, a->depth_var, a->disp, a->acc, a->weights, a->partial, N, S, fin, a->draw)
+            if (a->draw) { if (two) RT_LAUNCH(true, 2); else RT_LAUNCH(true, 1); }
+            else { if (two) RT_LAUNCH(false, 2); else RT_LAUNCH(false, 1); }
+#undef RT_LAUNCH
+            return check_launch(what);
+        }
+        MIPSF_REQUIRE(a->draw == nullptr, "draw: this device does not grant render_train_kernel's %u bytes of LDS", lds);
+    }
+    hipLaunchKernelGGL((render_fwd_kernel<true, true, RT_RPB>), grid, block, 0, s, a->raw, a->z_vals, a->target_rgb, a->target_d, rc,
+                       a->rgb, a->depth, a->depth_var, a->disp, a->acc, a->weights, a->partial, N, S, fin);
+    return check_launch(what);
+}
+
+extern "C" {
 
 // ONE entry point for the forward (round 5; include/mipsf.h): evaluation, training in two launches, training in one launch
 // (ticket), the training objective formed in the same launch (loss_weights / loss_total), a share of a ray-data-parallel
 // batch (sums).
 int mipsf_render_fwd(const mipsf_render_fwd_args* a_in, void* stream) {
-    MIPSF_REQUIRE(a_in != nullptr, "null argument block");
-    // (a block that ends before `draw` -- the first form of this ABI version -- is accepted: the field reads as null)
-    MIPSF_REQUIRE(a_in->struct_size == sizeof(mipsf_render_fwd_args) || a_in->struct_size == offsetof(mipsf_render_fwd_args, draw),
-                  "mipsf_render_fwd_args: struct_size %u, this library expects %u", a_in->struct_size,
-                  (unsigned)sizeof(mipsf_render_fwd_args));
-    mipsf_render_fwd_args a_copy = {};
-    memcpy(&a_copy, a_in, a_in->struct_size);
-    const mipsf_render_fwd_args* a = &a_copy;
-    const float* raw = a->raw; const float* z_vals = a->z_vals; const float* target_rgb = a->target_rgb; const float* target_d = a->target_d;
-    const uint32_t* counts = a->counts; const mipsf_render_cfg* cfg = a->cfg; float* rgb = a->rgb; float* depth = a->depth;
-    float* depth_var = a->depth_var; float* disp = a->disp; float* acc = a->acc; float* weights = a->weights; float* losses = a->losses;
-    float* partial = a->partial; const float* loss_weights = a->loss_weights; float* loss_total = a->loss_total;
-    uint32_t* ticket = a->ticket; const uint32_t N = a->N, S = a->S;
-    if (a->sums != nullptr) {
-        MIPSF_REQUIRE(losses == nullptr && loss_weights == nullptr && loss_total == nullptr && a->draw == nullptr,
-                      "sums: the losses of a share are finished by mipsf_loss_finalize_sums, not here");
-        return render_fwd_sums(raw, z_vals, target_rgb, target_d, counts, cfg, rgb, depth, depth_var, disp, acc, weights, partial,
-                               a->sums, ticket, N, S, stream);
-    }
-    MIPSF_REQUIRE((loss_weights == nullptr) == (loss_total == nullptr), "loss_weights and loss_total come together");
-    MIPSF_REQUIRE(loss_total == nullptr || losses != nullptr, "loss_total needs the training mode (losses)");
-    if (N == 0) return 0;
-    MIPSF_REQUIRE(cfg && raw && z_vals && rgb && depth, "null pointer");
-    MIPSF_REQUIRE(S >= 1 && S <= MAX_S, "samples per ray %u outside [1,%d]", S, MAX_S);
-    const RenderCfg rc = to_render_cfg(*cfg);
-    const dim3 grid((N + RAYS_PER_BLOCK - 1) / RAYS_PER_BLOCK), block(RAYS_PER_BLOCK * MIPSF_WAVE);
+    mipsf_render_fwd_args block_;
+    if (read_args(&block_, a_in, offsetof(mipsf_render_fwd_args, draw), "mipsf_render_fwd_args")) return 1;
+    const mipsf_render_fwd_args* a = &block_;
+    const uint32_t N = a->N, S = a->S;
     hipStream_t s = (hipStream_t)stream;
-    const LossFinalize fin = {counts, ticket, losses, loss_weights, loss_total, nullptr};
-    if (losses) {
-        MIPSF_REQUIRE(target_rgb && target_d && counts && partial, "training mode needs targets, counts, partial");
-        MIPSF_REQUIRE(a->draw == nullptr || (ticket && loss_total && S <= RT_MAX_S),
+    if (a->sums != nullptr) {
+        // A SHARE of a batch (ray-data-parallel training): the per-ray maps of this share and the nine fp64 sums its losses are
+        // made of -- {rgb_sq, depth_sq(valid), fs_sq, sdf_sq, fs_emd, sdf_emd, n_valid, n_front, n_band} -- in sums[9] (device).
+        // The caller adds the shares' sums (an all-reduce of 72 bytes) and finishes the losses with mipsf_loss_finalize_sums.
+        MIPSF_REQUIRE(a->losses == nullptr && a->loss_weights == nullptr && a->loss_total == nullptr && a->draw == nullptr,
+                      "sums: the losses of a share are finished by mipsf_loss_finalize_sums, not here");
+        MIPSF_REQUIRE(a->cfg && a->raw && a->z_vals && a->rgb && a->depth && a->target_rgb && a->target_d && a->counts && a->partial &&
+                      a->ticket, "null pointer");
+        MIPSF_REQUIRE(S >= 1 && S <= MAX_S, "samples per ray %u outside [1,%d]", S, MAX_S);
+        if (N == 0) {
+            if (hipMemsetAsync(a->sums, 0, 9 * sizeof(double), s) != hipSuccess) return 4;
+            return 0;
+        }
+        return launch_render_ticket(a, to_render_cfg(*a->cfg), {a->counts, a->ticket, nullptr, nullptr, nullptr, a->sums},
+                                    "render_fwd_sums", s);
+    }
+    MIPSF_REQUIRE((a->loss_weights == nullptr) == (a->loss_total == nullptr), "loss_weights and loss_total come together");
+    MIPSF_REQUIRE(a->loss_total == nullptr || a->losses != nullptr, "loss_total needs the training mode (losses)");
+    if (N == 0) return 0;
+    MIPSF_REQUIRE(a->cfg && a->raw && a->z_vals && a->rgb && a->depth, "null pointer");
+    MIPSF_REQUIRE(S >= 1 && S <= MAX_S, "samples per ray %u outside [1,%d]", S, MAX_S);
+    const RenderCfg rc = to_render_cfg(*a->cfg);
+    const dim3 grid((N + RAYS_PER_BLOCK - 1) / RAYS_PER_BLOCK), block(RAYS_PER_BLOCK * MIPSF_WAVE);
+    const LossFinalize fin = {a->counts, a->ticket, a->losses, a->loss_weights, a->loss_total, nullptr};
+    if (a->losses) {
+        MIPSF_REQUIRE(a->target_rgb && a->target_d && a->counts && a->partial, "training mode needs targets, counts, partial");
+        MIPSF_REQUIRE(a->draw == nullptr || (a->ticket && a->loss_total && S <= RT_MAX_S),
                       "draw: the one-launch form with the objective (ticket, loss_weights, loss_total) and S <= %u", RT_MAX_S);
-        if (ticket && S <= RT_MAX_S) {      // one launch, the ray read once; with `draw` also the backward of the objective
-            const int e = launch_render_train(raw, z_vals, target_rgb, target_d, rc, rgb, depth, depth_var, disp, acc, weights, partial,
-                                              N, S, fin, a->draw, s);
-            if (e > 0) return e;
-            if (e == 0) return check_launch("render_fwd");
-            MIPSF_REQUIRE(a->draw == nullptr, "draw: this device does not grant render_train_kernel's %u bytes of LDS", RT_RPB * S * 40u);
-        }
-        if (ticket) {       // one launch: the last workgroup finishes the losses
-            constexpr int RPB = 16;
-            hipLaunchKernelGGL((render_fwd_kernel<true, true, RPB>), dim3((N + RPB - 1) / RPB), dim3(RPB * MIPSF_WAVE), 0, s, raw,
-                               z_vals, target_rgb, target_d, rc, rgb, depth, depth_var, disp, acc, weights, partial, N, S, fin);
-            return check_launch("render_fwd");
-        }
-        hipLaunchKernelGGL((render_fwd_kernel<true, false, RAYS_PER_BLOCK>), grid, block, 0, s, raw, z_vals, target_rgb, target_d, rc, rgb,
-                           depth, depth_var, disp, acc, weights, partial, N, S, fin);
+        if (a->ticket) return launch_render_ticket(a, rc, fin, "render_fwd", s);
+        hipLaunchKernelGGL((render_fwd_kernel<true, false, RAYS_PER_BLOCK>), grid, block, 0, s, a->raw, a->z_vals, a->target_rgb,
+                           a->target_d, rc, a->rgb, a->depth, a->depth_var, a->disp, a->acc, a->weights, a->partial, N, S, fin);
         if (int e = check_launch("render_fwd")) return e;
-        hipLaunchKernelGGL(loss_finalize_kernel, dim3(1), dim3(LF_BLOCK), 0, s, partial, counts, rc.emd_w, losses, N, S,
-                           loss_weights, loss_total);
+        hipLaunchKernelGGL(loss_finalize_kernel, dim3(1), dim3(LF_BLOCK), 0, s, a->partial, a->counts, rc.emd_w, a->losses, N, S,
+                           a->loss_weights, a->loss_total);
         return check_launch("loss_finalize");
     }
-    hipLaunchKernelGGL((render_fwd_kernel<false, false, RAYS_PER_BLOCK>), grid, block, 0, s, raw, z_vals, target_rgb, target_d, rc, rgb, depth,
-                       depth_var, disp, acc, weights, partial, N, S, fin);
+    hipLaunchKernelGGL((render_fwd_kernel<false, false, RAYS_PER_BLOCK>), grid, block, 0, s, a->raw, a->z_vals, a->target_rgb, a->target_d,
+                       rc, a->rgb, a->depth, a->depth_var, a->disp, a->acc, a->weights, a->partial, N, S, fin);
     return check_launch("render_fwd");
-}
-
-// A SHARE of a batch (ray-data-parallel training): the per-ray maps of this share and the nine fp64 sums its losses are made
-// of -- {rgb_sq, depth_sq(valid), fs_sq, sdf_sq, fs_emd, sdf_emd, n_valid, n_front, n_band} -- in sums[9] (device).  The
-// caller adds the shares' sums (an all-reduce of 72 bytes) and finishes the losses with mipsf_loss_finalize_sums.
-static int render_fwd_sums(const float* raw, const float* z_vals, const float* target_rgb, const float* target_d,
-                           const uint32_t* counts, const mipsf_render_cfg* cfg, float* rgb, float* depth, float* depth_var,
-                           float* disp, float* acc, float* weights, float* partial, double* sums, uint32_t* ticket, uint32_t N,
-                           uint32_t S, void* stream) {
-    MIPSF_REQUIRE(cfg && raw && z_vals && rgb && depth && target_rgb && target_d && counts && partial && sums && ticket, "null pointer");
-    MIPSF_REQUIRE(S >= 1 && S <= MAX_S, "samples per ray %u outside [1,%d]", S, MAX_S);
-    hipStream_t s = (hipStream_t)stream;
-    if (N == 0) {
-        if (hipMemsetAsync(sums, 0, 9 * sizeof(double), s) != hipSuccess) return 4;
-        return 0;
-    }
-    const LossFinalize fin = {counts, ticket, nullptr, nullptr, nullptr, sums};
-    if (S <= RT_MAX_S) {
-        const int e = launch_render_train(raw, z_vals, target_rgb, target_d, to_render_cfg(*cfg), rgb, depth, depth_var, disp, acc, weights,
-                                          partial, N, S, fin, nullptr, s);
-        if (e > 0) return e;
-        if (e == 0) return check_launch("render_fwd_sums");
-    }
-    constexpr int RPB = 16;
-    hipLaunchKernelGGL((render_fwd_kernel<true, true, RPB>), dim3((N + RPB - 1) / RPB), dim3(RPB * MIPSF_WAVE), 0, s, raw, z_vals,
-                       target_rgb, target_d, to_render_cfg(*cfg), rgb, depth, depth_var, disp, acc, weights, partial, N, S, fin);
-    return check_launch("render_fwd_sums");
 }
 
 // losses[8] (and loss_total, as in mipsf_render_fwd) of a batch of N_total rays from its nine sums
@@ -1215,30 +982,23 @@ int mipsf_loss_finalize_sums(const double* sums, const mipsf_render_cfg* cfg, ui
 }
 
 int mipsf_render_bwd(const mipsf_render_bwd_args* a_in, void* stream) {
-    MIPSF_REQUIRE(a_in != nullptr, "null argument block");
-    MIPSF_REQUIRE(a_in->struct_size == sizeof(mipsf_render_bwd_args) || a_in->struct_size == offsetof(mipsf_render_bwd_args, flags),
-                  "mipsf_render_bwd_args: struct_size %u, this library expects %u", a_in->struct_size,
-                  (unsigned)sizeof(mipsf_render_bwd_args));
-    mipsf_render_bwd_args a_copy = {};
-    memcpy(&a_copy, a_in, a_in->struct_size);
-    const mipsf_render_bwd_args* a = &a_copy;
-    const float* raw = a->raw; const float* z_vals = a->z_vals; const float* target_rgb = a->target_rgb; const float* target_d = a->target_d;
-    const float* losses = a->losses; const mipsf_render_cfg* cfg = a->cfg; const float* g_losses = a->g_losses;
-    const float* g_total = a->g_total; const float* loss_weights = a->loss_weights; const float* g_rgb = a->g_rgb;
-    const float* g_depth = a->g_depth; float* draw = a->draw; const uint32_t N = a->N, S = a->S, N_norm = a->N_norm ? a->N_norm : a->N;
+    mipsf_render_bwd_args block_;
+    if (read_args(&block_, a_in, offsetof(mipsf_render_bwd_args, flags), "mipsf_render_bwd_args")) return 1;
+    const mipsf_render_bwd_args* a = &block_;
+    const uint32_t N = a->N, S = a->S, N_norm = a->N_norm ? a->N_norm : a->N;
     if (N == 0) return 0;
     MIPSF_REQUIRE(N_norm >= N, "N_norm = %u: the normalising ray count cannot be below this launch's %u rays", N_norm, N);
-    MIPSF_REQUIRE(cfg && raw && z_vals && draw, "null pointer");
+    MIPSF_REQUIRE(a->cfg && a->raw && a->z_vals && a->draw, "null pointer");
     MIPSF_REQUIRE(S >= 1 && S <= MAX_S, "samples per ray %u outside [1,%d]", S, MAX_S);
-    MIPSF_REQUIRE(g_total == nullptr || loss_weights != nullptr, "g_total needs the loss weights");
-    const int train = g_losses != nullptr || g_total != nullptr;
-    MIPSF_REQUIRE(!train || (target_rgb && target_d && losses), "training backward needs targets and losses");
+    MIPSF_REQUIRE(a->g_total == nullptr || a->loss_weights != nullptr, "g_total needs the loss weights");
+    const int train = a->g_losses != nullptr || a->g_total != nullptr;
+    MIPSF_REQUIRE(!train || (a->target_rgb && a->target_d && a->losses), "training backward needs targets and losses");
     const int keep_if_unit = (a->flags & MIPSF_RENDER_BWD_KEEP_IF_UNIT) != 0;
-    MIPSF_REQUIRE(!keep_if_unit || (g_total && !g_losses && !g_rgb && !g_depth && N_norm == N),
+    MIPSF_REQUIRE(!keep_if_unit || (a->g_total && !a->g_losses && !a->g_rgb && !a->g_depth && N_norm == N),
                   "KEEP_IF_UNIT: draw holds mipsf_render_fwd's gradient for g_total = 1 -- g_total must be the only gradient");
-    hipLaunchKernelGGL(render_bwd_kernel, dim3((N + RAYS_PER_BLOCK - 1) / RAYS_PER_BLOCK),
-                       dim3(RAYS_PER_BLOCK * MIPSF_WAVE), 0, (hipStream_t)stream, raw, z_vals, target_rgb, target_d,
-                       losses, to_render_cfg(*cfg), train, g_losses, g_rgb, g_depth, draw, N, S, g_total, loss_weights, N_norm, keep_if_unit);
+    hipLaunchKernelGGL(render_bwd_kernel, dim3((N + RAYS_PER_BLOCK - 1) / RAYS_PER_BLOCK), dim3(RAYS_PER_BLOCK * MIPSF_WAVE), 0,
+                       (hipStream_t)stream, a->raw, a->z_vals, a->target_rgb, a->target_d, a->losses, to_render_cfg(*a->cfg), train,
+                       a->g_losses, a->g_rgb, a->g_depth, a->draw, N, S, a->g_total, a->loss_weights, N_norm, keep_if_unit);
     return check_launch("render_bwd");
 }
 

@@ -757,15 +757,16 @@ def test_fused_adam_whole_step_in_one_launch(dev):
 def test_render_losses_finished_in_the_render_launch(dev):
     """mipsf_render_fwd with a ticket (the last workgroup of the render kernel finishes the losses, one launch) against the
     two-launch form mipsf_render_fwd: every output and all eight loss entries, at ray counts that leave the last
-    16-ray workgroup partly empty and that need one / several workgroups; the ticket is left at zero and repeated calls
+    16-ray workgroup partly empty and that need one / several workgroups, at sample counts on both sides of the one-launch
+    forms' threshold (S <= 128: render_train_kernel, above: render_fwd_kernel); the ticket is left at zero and repeated calls
     agree bit for bit."""
     import ctypes as C
     from mipsfusion_amd._lib import dptr, lib, stream_ptr
     torch.manual_seed(12)
     cfg = synth.config_headline()
-    S = 64
     rc = ops.make_render_cfg(cfg, cfg["mapping"]["bound"], cfg["mapping"]["localMLP_max_len"], 43, 21, 0.01)
-    for N in (1, 15, 16, 17, 1000, 4096):
+    # S = 64: render_train_kernel; S = 129, 256 (above its 128 samples): render_fwd_kernel's own ticket form
+    for S, N in [(64, n) for n in (1, 15, 16, 17, 1000, 4096)] + [(s, n) for s in (129, 256) for n in (1, 15, 16, 17, 1000)]:
         raw = torch.randn(N, S, 10, device=dev)
         raw[..., 3] = torch.linspace(1.0, -1.0, S, device=dev)[None] + 0.1 * torch.randn(N, S, device=dev)
         z = torch.sort(torch.rand(N, S, device=dev) * 4.0 + 0.1, dim=1).values
@@ -777,7 +778,8 @@ def test_render_losses_finished_in_the_render_launch(dev):
         def run(ticket):
             f = lambda *sh: torch.empty(sh, dtype=torch.float32, device=dev)      # noqa: E731
             outs = [f(N, 3), f(N), f(N), f(N), f(N)]
-            losses, partial, total = f(8), f(N * 8), f(1)
+            # (one ray's row of the ticket form is nine doubles: more than the 8 N floats of the two-launch form at N < 3)
+            losses, partial, total = f(8), f(_lib.buffer_size(_lib.SIZE_RENDER_PARTIAL, N)), f(1)
             a = _lib.RenderFwdArgs.new(N=N, S=S, raw=dptr(raw), z_vals=dptr(z), target_rgb=dptr(t_rgb), target_d=dptr(t_d),
                                        counts=dptr(counts, torch.int32), cfg=C.pointer(rc), rgb=dptr(outs[0]), depth=dptr(outs[1]),
                                        depth_var=dptr(outs[2]), disp=dptr(outs[3]), acc=dptr(outs[4]), losses=dptr(losses),
