@@ -43,6 +43,11 @@ int mipsf_topk_valid_scores(const float* depth, const float* draw, const uint8_t
  * arguments python refuses or n >= 2^32 (the caller then calls python's function, which raises or answers). */
 int mipsf_py_sample_range(mipsf_mt* g, int64_t n, int64_t k, int64_t* out, void* scratch);
 
+/* Manager.py:614-717 localMLP_expand_rule in float32, the host build of mipsfusion_amd/csrc/submap_dev.h (which the device
+ * compiles too): box and surface are (centre, length) [6], max_len [3], out (centre, length) [6].  Returns the case each axis
+ * took, axis a in bits 8a..8a+7 (0 contained, 1 full, 2 free, 3 positive side, 4 negative side, 5 both sides). */
+uint32_t mipsf_submap_expand_host(const float* box, const float* surface, const float* max_len, float* out);
+
 /* version of this interface */
 int mipsf_hostrng_abi(void);
 

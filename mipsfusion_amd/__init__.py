@@ -12,6 +12,7 @@ _SCENE_MESH = ("SubMap", "FusedVolume", "fuse_volume", "extract_scene_mesh", "su
 _POSE_CORRECTOR = ("cloud_from_rays", "estimate_normals", "registration_icp", "switch_pose_rectifying", "IcpResult")
 _POSE_GRAPH = ("adjacent_pairs", "global_ba_gate", "build_edges", "pose_graph_enqueue", "pose_graph_optimize", "rebase",
                "PoseGraphResult")
+_SUBMAP_MANAGER = ("SubmapManager", "Decision", "derive_schedule", "frame_stats_enqueue", "overlap_enqueue")
 
 
 def __getattr__(name):
@@ -28,4 +29,7 @@ def __getattr__(name):
     if name in _POSE_GRAPH:                 # closing a loop: the sub-map pose graph (mipsfusion_amd/pose_graph.py), the same way
         from . import pose_graph
         return getattr(pose_graph, name)
+    if name in _SUBMAP_MANAGER:             # sub-map decisions (mipsfusion_amd/submap_manager.py), the same way
+        from . import submap_manager
+        return getattr(submap_manager, name)
     raise AttributeError(f"module {__name__!r} has no attribute {name!r}")

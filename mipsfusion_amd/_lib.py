@@ -274,6 +274,28 @@ POSEGRAPH_SIGNATURES = {
 }
 
 
+# include/mipsf_submap.h (sub-map management: per-keyframe statistics and the overlap region)
+SUBMAP_MAX_BOXES, SUBMAP_MAX_TOP_KF, SUBMAP_HEADER_WORDS, SUBMAP_BOX_WORDS, SUBMAP_WORKSPACE_BYTES = 64, 10, 16, 12, 8192
+SUBMAP_RECORD_WORDS = SUBMAP_HEADER_WORDS + SUBMAP_MAX_BOXES * SUBMAP_BOX_WORDS
+SubmapFrameStatsArgs = _args("SubmapFrameStatsArgs", [("H", _CU), ("W", _CU), ("n_boxes", _CU), ("lat_a_h", _CU), ("lat_a_w", _CU),
+                                                      ("lat_b_h", _CU), ("lat_b_w", _CU), ("lat_c_h", _CU), ("lat_c_w", _CU),
+                                                      ("near", C.c_float), ("far", C.c_float), ("min_cr_len", C.c_float * 3),
+                                                      ("reserved", _CU), ("rows", _VP), ("pose", _VP), ("boxes", _VP),
+                                                      ("max_len", _VP), ("record", _VP), ("workspace", _VP)])
+SubmapOverlapArgs = _args("SubmapOverlapArgs", [("H", _CU), ("W", _CU), ("lat_h", _CU), ("lat_w", _CU), ("n_related", _CU), ("k", _CU),
+                                                ("n_slots", _CU), ("rows_per_slot", _CU), ("reserved", _CU),
+                                                ("fx", C.c_double), ("fy", C.c_double), ("cx", C.c_double), ("cy", C.c_double),
+                                                ("cam_W", C.c_double), ("cam_H", C.c_double), ("edge", C.c_double),
+                                                ("target_box", C.c_float * 6), ("rows", _VP), ("pose", _VP), ("table", _VP),
+                                                ("related_slots", _VP), ("related_poses", _VP), ("dist", _VP), ("top_poses", _VP),
+                                                ("top_kf_masks", _VP), ("mask_final", _VP), ("count", _VP), ("target_d", _VP),
+                                                ("rays_d_cam", _VP)])
+SUBMAP_SIGNATURES = {
+    "mipsf_submap_frame_stats": (_I, [C.POINTER(SubmapFrameStatsArgs), _P]),
+    "mipsf_submap_overlap": (_I, [C.POINTER(SubmapOverlapArgs), _P]),
+}
+
+
 def buffer_size(which: int, n: int = 0, a: int = 0, b: int = 0, meta=None) -> int:
     """mipsf_buffer_size: elements of a scratch / record buffer (SIZE_* above)."""
     v = lib().mipsf_buffer_size(which, n, a, b, C.byref(meta) if meta is not None else None)
@@ -296,7 +318,8 @@ def lib() -> C.CDLL:
         handle = C.CDLL(LIB_PATH)
         for name, (res, args) in list(SIGNATURES.items()) + (list(MESH_SIGNATURES.items())
                                        + list(FUSE_SIGNATURES.items()) + list(ICP_SIGNATURES.items())
-                                       + list(COMPACT_SIGNATURES.items()) + list(POSEGRAPH_SIGNATURES.items())):
+                                       + list(COMPACT_SIGNATURES.items()) + list(POSEGRAPH_SIGNATURES.items())
+                                       + list(SUBMAP_SIGNATURES.items())):
             fn = getattr(handle, name)
             fn.restype = res
             fn.argtypes = args
