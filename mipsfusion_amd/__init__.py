@@ -13,6 +13,8 @@ _POSE_CORRECTOR = ("cloud_from_rays", "estimate_normals", "registration_icp", "s
 _POSE_GRAPH = ("adjacent_pairs", "global_ba_gate", "build_edges", "pose_graph_enqueue", "pose_graph_optimize", "rebase",
                "PoseGraphResult")
 _SUBMAP_MANAGER = ("SubmapManager", "Decision", "derive_schedule", "frame_stats_enqueue", "overlap_enqueue")
+_EVALUATE = ("sample_surface", "nearest_distance", "distance_stats", "reconstruction_metrics", "cull_to_views", "ReconMetrics",
+             "DistanceStats")
 
 
 def __getattr__(name):
@@ -32,4 +34,7 @@ def __getattr__(name):
     if name in _SUBMAP_MANAGER:             # sub-map decisions (mipsfusion_amd/submap_manager.py), the same way
         from . import submap_manager
         return getattr(submap_manager, name)
+    if name in _EVALUATE:                   # scoring a mesh against ground truth (mipsfusion_amd/evaluate.py), the same way
+        from . import evaluate
+        return getattr(evaluate, name)
     raise AttributeError(f"module {__name__!r} has no attribute {name!r}")

@@ -296,6 +296,35 @@ SUBMAP_SIGNATURES = {
 }
 
 
+# include/mipsf_eval.h (scoring a mesh against ground truth: surface samples, nearest neighbour without a radius, statistics)
+EVAL_MAX_FACES, EVAL_MAX_SAMPLES = 1 << 30, 1 << 27
+EVAL_WS_SAMPLE, EVAL_WS_STATS = 1, 2
+EVAL_OK, EVAL_NO_AREA, EVAL_AREA_OVERFLOW = 0, 1, 2
+EVAL_SAMPLE_RECORD_BYTES, EVAL_STATS_RECORD_BYTES = 32, 64
+
+
+class EvalSampleRecord(C.Structure):
+    _fields_ = [("area", C.c_double), ("total_units", C.c_uint64), ("status", C.c_uint32), ("reserved", C.c_uint32 * 3)]
+
+
+class EvalStatsRecord(C.Structure):
+    _fields_ = [("sum_d", C.c_double), ("sum_d2", C.c_double), ("max_d2", C.c_double), ("within", C.c_uint64), ("finite", C.c_uint64),
+                ("reserved", C.c_uint64 * 3)]
+
+
+EvalSampleArgs = _args("EvalSampleArgs", [("V", _CU), ("F", _CU), ("n", _CU), ("seed", _CU), ("vertices", _VP), ("faces", _VP),
+                                          ("points", _VP), ("face_of", _VP), ("record", _VP), ("workspace", _VP)])
+EvalNearestArgs = _args("EvalNearestArgs", [("n_source", _CU), ("n_target", _CU), ("max_cells", _CU), ("source", _VP), ("grid", _VP),
+                                            ("index", _VP), ("d2", _VP)])
+EvalStatsArgs = _args("EvalStatsArgs", [("n", _CU), ("d2", _VP), ("threshold", C.c_double), ("record", _VP), ("workspace", _VP)])
+EVAL_SIGNATURES = {
+    "mipsf_eval_workspace_bytes": (_U64, [_I, _U32]),
+    "mipsf_eval_sample": (_I, [C.POINTER(EvalSampleArgs), _P]),
+    "mipsf_eval_nearest": (_I, [C.POINTER(EvalNearestArgs), _P]),
+    "mipsf_eval_stats": (_I, [C.POINTER(EvalStatsArgs), _P]),
+}
+
+
 def buffer_size(which: int, n: int = 0, a: int = 0, b: int = 0, meta=None) -> int:
     """mipsf_buffer_size: elements of a scratch / record buffer (SIZE_* above)."""
     v = lib().mipsf_buffer_size(which, n, a, b, C.byref(meta) if meta is not None else None)
@@ -319,7 +348,7 @@ def lib() -> C.CDLL:
         for name, (res, args) in list(SIGNATURES.items()) + (list(MESH_SIGNATURES.items())
                                        + list(FUSE_SIGNATURES.items()) + list(ICP_SIGNATURES.items())
                                        + list(COMPACT_SIGNATURES.items()) + list(POSEGRAPH_SIGNATURES.items())
-                                       + list(SUBMAP_SIGNATURES.items())):
+                                       + list(SUBMAP_SIGNATURES.items()) + list(EVAL_SIGNATURES.items())):
             fn = getattr(handle, name)
             fn.restype = res
             fn.argtypes = args

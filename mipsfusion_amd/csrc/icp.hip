@@ -8,23 +8,18 @@
 // order of the points inside a cell (the scatter's integer atomics decide it) reaches a result.  Sums that feed a result are
 // added in a fixed order: lane -> wave (cross-lane moves) -> block partials in a buffer -> one finishing wave.  The library is
 // built with -ffp-contract=off.
-#include "common.h"
+#include "icp_grid.h"
 #include "../../include/mipsf_icp.h"
-
-#include <math.h>
 
 namespace mipsf {
 namespace {
 
-constexpr int TPB = 256;
+constexpr int TPB = GRID_TPB;
 constexpr int WAVES = TPB / MIPSF_WAVE;
-constexpr int SCAN_TILE = TPB * 4;       // entries one block scans
+constexpr int SCAN_TILE = GRID_SCAN_TILE; // entries one block scans
 constexpr int KNN = MIPSF_ICP_KNN;
 constexpr int NSUM = 29;                 // 21 (upper triangle of J^T J) + 6 (J^T r) + pairs + sum of squared distances
 constexpr int NSUM_PAD = 32;
-
-inline uint32_t blocks_for(uint64_t n, uint32_t per = TPB) { return (uint32_t)((n + per - 1) / per); }
-inline uint64_t align16(uint64_t v) { return (v + 15u) & ~(uint64_t)15u; }
 
 // ------------------------------------------------------------------------------------------------ exclusive scan of uint32
 __device__ __forceinline__ uint32_t wave_excl_scan(uint32_t v, uint32_t& total) {
@@ -150,44 +145,7 @@ MIPSF_SINGLE_FP32 __global__ void __launch_bounds__(TPB) cloud_emit_kernel(Cloud
     }
 }
 
-// ------------------------------------------------------------------------------------------------ grid
-struct GridHdr {
-    double origin[3];
-    double edge;
-    uint32_t dims[3];
-    uint32_t ncells;
-    uint32_t pad[4];
-};
-static_assert(sizeof(GridHdr) == 64, "GridHdr");
-
-struct GridLayout {
-    uint64_t hdr, bbox, start, cnt, bsum, sorted, bytes;
-};
-
-GridLayout grid_layout(uint32_t n, uint32_t cells) {
-    GridLayout L;
-    L.hdr = 0;
-    L.bbox = 128;
-    L.start = align16(L.bbox + (uint64_t)blocks_for(n ? n : 1) * 6 * sizeof(float));
-    L.cnt = align16(L.start + ((uint64_t)cells + 1) * 4);
-    L.bsum = align16(L.cnt + ((uint64_t)cells + 1) * 4);
-    L.sorted = align16(L.bsum + (uint64_t)blocks_for((uint64_t)cells + 1, SCAN_TILE) * 4);
-    L.bytes = L.sorted + (uint64_t)(n ? n : 1) * 16;
-    return L;
-}
-
-struct Grid {       // device view
-    const GridHdr* hdr;
-    const uint32_t* start;
-    const float4* sorted;
-};
-
-Grid grid_view(const void* blob, uint32_t n, uint32_t cells) {
-    const GridLayout L = grid_layout(n, cells);
-    const char* b = (const char*)blob;
-    return Grid{(const GridHdr*)(b + L.hdr), (const uint32_t*)(b + L.start), (const float4*)(b + L.sorted)};
-}
-
+// ------------------------------------------------------------------------------------------------ grid (its layout: icp_grid.h)
 MIPSF_SINGLE_FP32 __global__ void __launch_bounds__(TPB) bbox_partial_kernel(const float* __restrict__ pts, uint32_t n,
                                                                              float* __restrict__ part) {
     __shared__ float sm[WAVES][6];
@@ -266,12 +224,6 @@ MIPSF_SINGLE_FP32 __global__ void __launch_bounds__(MIPSF_WAVE) bbox_finish_kern
     h->ncells = dims[0] * dims[1] * dims[2];
 }
 
-// cell coordinate of x along an axis, clamped into the grid (NaN -> 0)
-__device__ __forceinline__ uint32_t cell_of(double x, double origin, double edge, uint32_t dim) {
-    const double f = floor((x - origin) / edge);
-    return f >= (double)(dim - 1) ? dim - 1 : (f > 0.0 ? (uint32_t)f : 0u);
-}
-
 __device__ __forceinline__ uint32_t cell_index(const GridHdr& h, double x, double y, double z) {
     const uint32_t cx = cell_of(x, h.origin[0], h.edge, h.dims[0]), cy = cell_of(y, h.origin[1], h.edge, h.dims[1]),
                    cz = cell_of(z, h.origin[2], h.edge, h.dims[2]);
@@ -297,11 +249,6 @@ MIPSF_SINGLE_FP32 __global__ void __launch_bounds__(TPB) bin_scatter_kernel(cons
     const uint32_t c = cell_index(h, x, y, z);
     const uint32_t slot = start[c] + (atomicSub(&cnt[c], 1u) - 1u);
     if (slot < n) sorted[slot] = make_float4(x, y, z, __uint_as_float(i));
-}
-
-__device__ __forceinline__ double dist2(double qx, double qy, double qz, const float4& v) {
-    const double dx = qx - (double)v.x, dy = qy - (double)v.y, dz = qz - (double)v.z;
-    return (dx * dx + dy * dy) + dz * dz;
 }
 
 struct Best {

@@ -87,6 +87,73 @@ def render_rooms_frame(room_a, room_b, door, c2w: torch.Tensor, H, W, fx, fy, cx
             "direction": dirs}
 
 
+def _quad(corners, inward):
+    """two triangles of the rectangle `corners` (4 points in order around it), wound so that (B-A) x (C-A) points along `inward`"""
+    c = np.asarray(corners, dtype=np.float64)
+    if np.dot(np.cross(c[1] - c[0], c[2] - c[0]), inward) < 0:
+        c = c[::-1]
+    return [c[0], c[1], c[2]], [c[0], c[2], c[3]]
+
+
+def _rect(axis, at, lo, hi, inward_sign):
+    """the rectangle on the plane x[axis] = at between lo and hi (3-vectors; their entry `axis` is ignored), normal along
+    inward_sign * e_axis"""
+    a, b = [d for d in range(3) if d != axis]
+    corners = []
+    for ua, ub in ((lo[a], lo[b]), (hi[a], lo[b]), (hi[a], hi[b]), (lo[a], hi[b])):
+        p = np.zeros(3)
+        p[axis], p[a], p[b] = at, ua, ub
+        corners.append(p)
+    n = np.zeros(3)
+    n[axis] = inward_sign
+    return _quad(corners, n)
+
+
+def _soup_to_mesh(tris):
+    """triangles [T,3,3] -> (vertices float64 [V,3] without repeats, faces int64 [T,3])"""
+    t = np.asarray(tris, dtype=np.float64).reshape(-1, 3)
+    vertices, inverse = np.unique(t, axis=0, return_inverse=True)
+    return vertices, inverse.reshape(-1, 3).astype(np.int64)
+
+
+def _box_walls(lo, hi, skip=()):
+    tris = []
+    for axis in range(3):
+        for at, sign in ((lo[axis], 1.0), (hi[axis], -1.0)):
+            if (axis, sign) not in skip:
+                tris += _rect(axis, at, lo, hi, sign)
+    return tris
+
+
+def box_room_mesh(bound, shrink=0.3):
+    """Ground truth of ``render_box_frame``: the six walls of the room as 12 triangles, normals pointing into the room ->
+    (vertices float64 [8,3], faces int64 [12,3]).  ``lo`` and ``hi`` are formed in float32 as the renderer forms them and then
+    widened, so the mesh lies exactly on the planes the rays hit."""
+    bound = torch.as_tensor(bound, dtype=torch.float32)
+    lo, hi = (bound[:, 0] + shrink).double().numpy(), (bound[:, 1] - shrink).double().numpy()
+    return _soup_to_mesh(_box_walls(lo, hi))
+
+
+def two_rooms_mesh(rooms=None):
+    """Ground truth of ``render_rooms_frame`` for a dictionary like ``TWO_ROOMS``: both rooms' walls, normals pointing into
+    their room -> (vertices float64 [V,3], faces int64 [F,3]).  The shared wall z = room_a[2][1] is there ONCE PER ROOM (two
+    coincident copies with opposite normals: each room sees its own side of it), each copy without the door: the door reaches
+    the floor (its y0 is the rooms'), so a copy is three rectangles.  Area = both boxes - 2 * door.  Coordinates pass through
+    float32 as the renderer's do."""
+    rooms = TWO_ROOMS if rooms is None else rooms
+    f32 = lambda v: torch.as_tensor(v, dtype=torch.float32).double().numpy()      # noqa: E731
+    A, B, door = f32(rooms["room_a"]), f32(rooms["room_b"]), f32(rooms["door"])
+    if A[2, 1] != B[2, 0] or door[1, 0] != A[1, 0] or door[1, 0] != B[1, 0]:
+        raise ValueError("two_rooms_mesh: the rooms must share the wall z = room_a[2][1] and the door must reach the floor")
+    tris = _box_walls(A[:, 0], A[:, 1], skip=((2, -1.0),)) + _box_walls(B[:, 0], B[:, 1], skip=((2, 1.0),))
+    z = A[2, 1]
+    for box, sign in ((A, -1.0), (B, 1.0)):
+        x_lo, x_hi, y_lo, y_hi = box[0, 0], box[0, 1], box[1, 0], box[1, 1]
+        for (xa, xb, ya, yb) in ((x_lo, door[0, 0], y_lo, y_hi), (door[0, 1], x_hi, y_lo, y_hi), (door[0, 0], door[0, 1], door[1, 1], y_hi)):
+            tris += _rect(2, z, np.array([xa, ya, 0.0]), np.array([xb, yb, 0.0]), sign)
+    return _soup_to_mesh(tris)
+
+
 def config_two_rooms() -> dict:
     """BASELINE config 3 workload: the reference's FastCaMo-synth settings as shipped (S = 50 + 25, 1800 + 800 rays, 5 RO
     rounds, 10 tracking / 15 mapping iterations, 500 initialisation iterations per sub-map, 15 pose-only iterations after a
