@@ -15,6 +15,7 @@ _POSE_GRAPH = ("adjacent_pairs", "global_ba_gate", "build_edges", "pose_graph_en
 _SUBMAP_MANAGER = ("SubmapManager", "Decision", "derive_schedule", "frame_stats_enqueue", "overlap_enqueue")
 _EVALUATE = ("sample_surface", "nearest_distance", "distance_stats", "reconstruction_metrics", "cull_to_views", "ReconMetrics",
              "DistanceStats")
+_MESH_RENDER = ("render_mesh_depth", "depth_l1", "visible_points", "DepthMetrics")
 
 
 def __getattr__(name):
@@ -37,4 +38,7 @@ def __getattr__(name):
     if name in _EVALUATE:                   # scoring a mesh against ground truth (mipsfusion_amd/evaluate.py), the same way
         from . import evaluate
         return getattr(evaluate, name)
+    if name in _MESH_RENDER:                # a mesh as depth images, depth L1, occlusion (mipsfusion_amd/mesh_render.py), the same way
+        from . import mesh_render
+        return getattr(mesh_render, name)
     raise AttributeError(f"module {__name__!r} has no attribute {name!r}")

@@ -325,6 +325,35 @@ EVAL_SIGNATURES = {
 }
 
 
+# include/mipsf_raster.h (a mesh as per-pixel depth from a batch of poses; depth L1; the occlusion test of the culling)
+RASTER_TILE, RASTER_MAX_FACES, RASTER_MAX_SIDE, RASTER_MAX_PIXELS, RASTER_MAX_ITEMS = 8, 1 << 30, 8192, 1 << 30, 0x7FFFFFFF
+RASTER_WS_DEPTH, RASTER_WS_L1 = 1, 2
+RASTER_STAGE_COUNT, RASTER_STAGE_SCAN, RASTER_STAGE_RASTER, RASTER_STAGE_RESOLVE = 1, 2, 4, 8
+RASTER_L1_RECORD_BYTES = 64
+
+
+class RasterL1Record(C.Structure):
+    _fields_ = [("sum_all", C.c_double), ("sum_both", C.c_double), ("both", C.c_uint64), ("rec_only", C.c_uint64),
+                ("gt_only", C.c_uint64), ("neither", C.c_uint64), ("reserved", C.c_uint64 * 2)]
+
+
+RasterDepthArgs = _args("RasterDepthArgs", [("V", _CU), ("F", _CU), ("n", _CU), ("H", _CU), ("W", _CU), ("stages", _CU), ("reserved", _CU),
+                                            ("fx", C.c_double), ("fy", C.c_double), ("cx", C.c_double), ("cy", C.c_double),
+                                            ("near", C.c_double), ("far", C.c_double), ("vertices", _VP), ("faces", _VP),
+                                            ("poses", _VP), ("depth", _VP), ("face", _VP), ("workspace", _VP)])
+RasterL1Args = _args("RasterL1Args", [("n", _CU), ("H", _CU), ("W", _CU), ("a", _VP), ("b", _VP), ("records", _VP), ("workspace", _VP)])
+RasterVisibleArgs = _args("RasterVisibleArgs", [("m", _CU), ("n", _CU), ("H", _CU), ("W", _CU), ("reserved", _CU),
+                                                ("fx", C.c_double), ("fy", C.c_double), ("cx", C.c_double), ("cy", C.c_double),
+                                                ("edge", C.c_double), ("eps", C.c_double), ("points", _VP), ("depth", _VP),
+                                                ("poses", _VP), ("max_depth", _VP), ("seen", _VP)])
+RASTER_SIGNATURES = {
+    "mipsf_raster_workspace_bytes": (_U64, [_I, _U32, _U32, _U32, _U32]),
+    "mipsf_raster_depth": (_I, [C.POINTER(RasterDepthArgs), _P]),
+    "mipsf_raster_l1": (_I, [C.POINTER(RasterL1Args), _P]),
+    "mipsf_raster_visible": (_I, [C.POINTER(RasterVisibleArgs), _P]),
+}
+
+
 def buffer_size(which: int, n: int = 0, a: int = 0, b: int = 0, meta=None) -> int:
     """mipsf_buffer_size: elements of a scratch / record buffer (SIZE_* above)."""
     v = lib().mipsf_buffer_size(which, n, a, b, C.byref(meta) if meta is not None else None)
@@ -348,7 +377,8 @@ def lib() -> C.CDLL:
         for name, (res, args) in list(SIGNATURES.items()) + (list(MESH_SIGNATURES.items())
                                        + list(FUSE_SIGNATURES.items()) + list(ICP_SIGNATURES.items())
                                        + list(COMPACT_SIGNATURES.items()) + list(POSEGRAPH_SIGNATURES.items())
-                                       + list(SUBMAP_SIGNATURES.items()) + list(EVAL_SIGNATURES.items())):
+                                       + list(SUBMAP_SIGNATURES.items()) + list(EVAL_SIGNATURES.items())
+                                       + list(RASTER_SIGNATURES.items())):
             fn = getattr(handle, name)
             fn.restype = res
             fn.argtypes = args

@@ -7,7 +7,8 @@ surface, form means and the share below a threshold).  Upstream has no evaluatio
     nearest_distance        the exact nearest neighbour of every source point, with no radius
     distance_stats          squared distances -> sums, maximum and counts, one read-back
     reconstruction_metrics  the three above on both meshes -> ReconMetrics
-    cull_to_views           the faces some keyframe saw (applied to both meshes before scoring, as the published protocol does)
+    cull_to_views           the faces some keyframe saw (applied to both meshes before scoring, as the published protocol does),
+                            with the protocol's occlusion test on request (mesh_render.py)
 
 The samples and the neighbours EQUAL those of the float64 restatement in tests/eval_cpu.py: areas are integers, the random numbers
 a counter-based integer hash, the distances the float64 expression of include/mipsf_icp.h ordered by (distance, index).
@@ -203,15 +204,27 @@ def reconstruction_metrics(mesh_rec, mesh_gt, n_samples: int = 200_000, threshol
                         acc.max_d, comp.max_d, area_rec, area_gt, int(n_samples), float(threshold))
 
 
-def cull_to_views(mesh, kf_c2w, kf_max_depth, K, W, H, edge=20):
-    """The faces whose three vertices some keyframe saw (scene_mesh.point_mask: inside the image by `edge` pixels, in front of
-    the camera, nearer than the keyframe's largest depth) -> mesh.Mesh with the same vertices.  No occlusion test, as upstream's
-    culling has none."""
+def cull_to_views(mesh, kf_c2w, kf_max_depth, K, W, H, edge=20, occlusion=False, occluder=None, eps=None):
+    """The faces whose three vertices some keyframe saw -> mesh.Mesh with the same vertices.
+    occlusion=False (upstream's culling, which has no occlusion test): scene_mesh.point_mask -- inside the image by `edge` pixels,
+    in front of the camera, nearer than the keyframe's largest depth.
+    occlusion=True (the published protocol): mesh_render.visible_points -- the same frustum test in float64 and, besides, not more
+    than `eps` metres behind the depth image of `occluder` rendered from that keyframe (the mesh itself when occluder is None; the
+    ground truth when both meshes are to be culled alike).  `eps` has no default: the published value is not on record here."""
     from . import mesh as mesh_mod
     from . import scene_mesh
     vertices, faces = _split(mesh)
     v, f = _mesh_tensors(vertices, faces)
-    seen = scene_mesh.point_mask(v, kf_c2w, kf_max_depth, K, W, H, edge)
+    if occlusion:
+        from . import mesh_render
+        if eps is None:
+            raise ValueError("cull_to_views(occlusion=True) needs eps: how far behind the rendered depth a vertex still counts as seen")
+        depth, _ = mesh_render.render_mesh_depth(mesh if occluder is None else occluder, kf_c2w, K, H, W)
+        seen = mesh_render.visible_points(v, depth, kf_c2w, kf_max_depth, K, edge, eps)
+    else:
+        if occluder is not None or eps is not None:
+            raise ValueError("cull_to_views: occluder and eps belong to occlusion=True")
+        seen = scene_mesh.point_mask(v, kf_c2w, kf_max_depth, K, W, H, edge)
     fl = f.to(torch.int64)
     ok = (fl >= 0).all(1) & (fl < v.shape[0]).all(1)
     keep = torch.zeros(f.shape[0], dtype=torch.bool, device=f.device)
