@@ -55,6 +55,16 @@ uint64_t mcubes_weld_words(uint32_t T);
         }                                        \
     } while (0)
 
+// the head of every entry point that takes an argument block: `a` is there and was built against this library's `type`
+#define MIPSF_ARGS(a, type, name)                                                                                        \
+    MIPSF_REQUIRE((a) != nullptr, "%s: null argument block", name);                                                      \
+    MIPSF_REQUIRE((a)->struct_size == sizeof(type), #type ": struct_size %u, this library expects %u", (a)->struct_size, \
+                  (unsigned)sizeof(type))
+
+// blocks of `per` items that cover n items
+inline uint32_t blocks_for(uint64_t n, uint32_t per) { return (uint32_t)((n + per - 1) / per); }
+inline uint64_t align16(uint64_t v) { return (v + 15u) & ~(uint64_t)15u; }
+
 // level table handed to kernels by value
 struct GridLevels {
     uint32_t n_levels;

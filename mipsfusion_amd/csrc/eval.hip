@@ -6,6 +6,7 @@
 // so their prefix sum is the same in any order; everything else a result depends on is float64, one operation at a time (the
 // library is built with -ffp-contract=off), which tests/eval_cpu.py restates word for word.  Sums are added in a fixed order: lane
 // -> wave (cross-lane moves) -> block partials in a buffer -> one finishing wave.
+#include "block_dev.h"
 #include "icp_grid.h"
 #include "../../include/mipsf_eval.h"
 #include "../../include/mipsf_icp.h"
@@ -15,47 +16,9 @@ namespace {
 
 constexpr int TPB = 256;
 constexpr int WAVES = TPB / MIPSF_WAVE;
-constexpr int SCAN_TILE = TPB * 4;           // faces one block scans
+constexpr int SCAN_TILE = TPB * SCAN_ITEMS;  // faces one block scans
 constexpr uint32_t STATS_MAX_BLOCKS = 1024;
 constexpr uint64_t UNITS_CAP = 1ull << 63;   // a total of this many units or more is refused
-
-// ------------------------------------------------------------------------------------------------ sums and scans of uint64
-__device__ __forceinline__ uint64_t wave_sum_u64(uint64_t v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += (uint64_t)__shfl_xor((unsigned long long)v, o, 64);
-    return v;
-}
-
-// the sum over the TPB threads of a block, in every thread; sm holds WAVES words
-__device__ __forceinline__ uint64_t block_sum_u64(uint64_t v, uint64_t* sm) {
-    v = wave_sum_u64(v);
-    if ((threadIdx.x & 63) == 0) sm[threadIdx.x >> 6] = v;
-    __syncthreads();
-    uint64_t total = 0;
-#pragma unroll
-    for (int i = 0; i < WAVES; ++i) total += sm[i];
-    __syncthreads();
-    return total;
-}
-
-// exclusive scan over the TPB threads of a block; sm holds WAVES words
-__device__ __forceinline__ uint64_t block_excl_scan_u64(uint64_t v, uint64_t* sm) {
-    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-    uint64_t inc = v;
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-        const uint64_t t = (uint64_t)__shfl_up((unsigned long long)inc, o, 64);
-        if (lane >= o) inc += t;
-    }
-    if (lane == 63) sm[w] = inc;
-    __syncthreads();
-    uint64_t base = 0;
-#pragma unroll
-    for (int i = 0; i < WAVES; ++i)
-        if (i < w) base += sm[i];
-    __syncthreads();
-    return base + (inc - v);
-}
 
 // ------------------------------------------------------------------------------------------------ sampler
 struct MeshView {
@@ -104,16 +67,16 @@ __device__ __forceinline__ uint64_t face_units(const MeshView& m, uint32_t f) {
 MIPSF_SINGLE_FP32 __global__ void __launch_bounds__(TPB) eval_units_kernel(MeshView m, uint64_t* __restrict__ cum, uint64_t* __restrict__ tiles,
                                                                            uint32_t nb) {
     __shared__ uint64_t sm[WAVES];
-    const uint64_t base = (uint64_t)blockIdx.x * SCAN_TILE + threadIdx.x * 4;
+    const uint64_t base = (uint64_t)blockIdx.x * SCAN_TILE + threadIdx.x * SCAN_ITEMS;
     uint64_t s = 0, hi = 0, lo = 0;
 #pragma unroll
-    for (int k = 0; k < 4; ++k)
+    for (int k = 0; k < SCAN_ITEMS; ++k)
         if (base + k < m.F) {
             const uint64_t u = face_units(m, (uint32_t)(base + k));
             cum[base + k] = u;
             s += u, hi += u >> 32, lo += u & 0xffffffffull;
         }
-    s = block_sum_u64(s, sm), hi = block_sum_u64(hi, sm), lo = block_sum_u64(lo, sm);
+    s = block_reduce<WAVES>(s, sm, Add()), hi = block_reduce<WAVES>(hi, sm, Add()), lo = block_reduce<WAVES>(lo, sm, Add());
     if (threadIdx.x == 0) tiles[blockIdx.x] = s, tiles[nb + blockIdx.x] = hi, tiles[2 * (size_t)nb + blockIdx.x] = lo;
 }
 
@@ -121,18 +84,12 @@ MIPSF_SINGLE_FP32 __global__ void __launch_bounds__(TPB) eval_units_kernel(MeshV
 // each), so hi + (lo >> 32) is the true total >> 32.
 __global__ void __launch_bounds__(TPB) eval_scan_top_kernel(uint64_t* tiles, uint32_t nb, mipsf_eval_sample_record* rec) {
     __shared__ uint64_t sm[WAVES];
-    const uint32_t chunk = (nb + TPB - 1) / TPB;
-    const uint32_t lo_i = min(threadIdx.x * chunk, nb), hi_i = min(lo_i + chunk, nb);
-    uint64_t s = 0, hi = 0, lo = 0;
-    for (uint32_t i = lo_i; i < hi_i; ++i) s += tiles[i], hi += tiles[nb + i], lo += tiles[2 * (size_t)nb + i];
-    uint64_t run = block_excl_scan_u64(s, sm);
-    for (uint32_t i = lo_i; i < hi_i; ++i) {
-        const uint64_t t = tiles[i];
-        tiles[i] = run;
-        run += t;
-    }
-    const uint64_t total = block_sum_u64(s, sm);
-    hi = block_sum_u64(hi, sm), lo = block_sum_u64(lo, sm);
+    uint32_t lo_i, hi_i;
+    scan_top_range<WAVES>(nb, lo_i, hi_i);
+    uint64_t hi = 0, lo = 0;
+    for (uint32_t i = lo_i; i < hi_i; ++i) hi += tiles[nb + i], lo += tiles[2 * (size_t)nb + i];
+    const uint64_t total = scan_top<WAVES>(tiles, nb, sm);
+    hi = block_reduce<WAVES>(hi, sm, Add()), lo = block_reduce<WAVES>(lo, sm, Add());
     if (threadIdx.x == 0) {
         const bool over = hi + (lo >> 32) >= (UNITS_CAP >> 32);
         rec->total_units = total;
@@ -145,19 +102,7 @@ __global__ void __launch_bounds__(TPB) eval_scan_top_kernel(uint64_t* tiles, uin
 // cum: the faces' units in, their inclusive prefix sum out
 __global__ void __launch_bounds__(TPB) eval_scan_apply_kernel(uint64_t* cum, uint32_t F, const uint64_t* __restrict__ tiles) {
     __shared__ uint64_t sm[WAVES];
-    const uint64_t base = (uint64_t)blockIdx.x * SCAN_TILE + threadIdx.x * 4;
-    uint64_t v[4], s = 0;
-#pragma unroll
-    for (int k = 0; k < 4; ++k) {
-        v[k] = base + k < F ? cum[base + k] : 0ull;
-        s += v[k];
-    }
-    uint64_t run = block_excl_scan_u64(s, sm) + tiles[blockIdx.x];
-#pragma unroll
-    for (int k = 0; k < 4; ++k) {
-        run += v[k];
-        if (base + k < F) cum[base + k] = run;
-    }
+    scan_apply<WAVES, true>(cum, F, tiles, cum, sm);
 }
 
 __device__ __forceinline__ double uniform24(uint32_t seed, uint32_t k, uint32_t which) {
@@ -270,9 +215,7 @@ static_assert(sizeof(StatsPartial) == 64 && sizeof(mipsf_eval_stats_record) == 6
 static_assert(sizeof(mipsf_eval_sample_record) == 32, "sample record");
 
 __device__ __forceinline__ double wave_max_d(double v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v = fmax(v, __shfl_xor(v, o, 64));
-    return v;
+    return wave_reduce(v, [](double a, double b) { return fmax(a, b); });
 }
 
 // block b, thread t takes entries (b*TPB + t) + j * (blocks*TPB); butterfly over the wave; waves in ascending order
@@ -324,11 +267,6 @@ inline uint32_t stats_blocks(uint32_t n) { return n ? min(blocks_for(n, TPB), ST
 
 using namespace mipsf;
 
-#define EVAL_ARGS(a, type, name)                                                                                         \
-    MIPSF_REQUIRE((a) != nullptr, name ": null argument block");                                                         \
-    MIPSF_REQUIRE((a)->struct_size == sizeof(type), #type ": struct_size %u, this library expects %u", (a)->struct_size, \
-                  (unsigned)sizeof(type))
-
 extern "C" uint64_t mipsf_eval_workspace_bytes(int which, uint32_t n) {
     switch (which) {
         case MIPSF_EVAL_WS_SAMPLE:
@@ -341,7 +279,7 @@ extern "C" uint64_t mipsf_eval_workspace_bytes(int which, uint32_t n) {
 }
 
 extern "C" int mipsf_eval_sample(const mipsf_eval_sample_args* a, void* stream) {
-    EVAL_ARGS(a, mipsf_eval_sample_args, "mipsf_eval_sample");
+    MIPSF_ARGS(a, mipsf_eval_sample_args, "mipsf_eval_sample");
     MIPSF_REQUIRE(a->F > 0, "mipsf_eval_sample: a mesh without faces has no surface to sample");
     MIPSF_REQUIRE(a->F <= MIPSF_EVAL_MAX_FACES, "mipsf_eval_sample: %u faces, at most %u", a->F, MIPSF_EVAL_MAX_FACES);
     MIPSF_REQUIRE(a->n <= MIPSF_EVAL_MAX_SAMPLES, "mipsf_eval_sample: %u samples, at most %u", a->n, MIPSF_EVAL_MAX_SAMPLES);
@@ -363,7 +301,7 @@ extern "C" int mipsf_eval_sample(const mipsf_eval_sample_args* a, void* stream) 
 }
 
 extern "C" int mipsf_eval_nearest(const mipsf_eval_nearest_args* a, void* stream) {
-    EVAL_ARGS(a, mipsf_eval_nearest_args, "mipsf_eval_nearest");
+    MIPSF_ARGS(a, mipsf_eval_nearest_args, "mipsf_eval_nearest");
     if (a->n_source == 0) return 0;
     MIPSF_REQUIRE(a->source && a->grid && a->index && a->d2, "mipsf_eval_nearest: null pointer");
     MIPSF_REQUIRE(((uintptr_t)a->grid & 15u) == 0, "mipsf_eval_nearest: grid not 16-byte aligned");
@@ -375,7 +313,7 @@ extern "C" int mipsf_eval_nearest(const mipsf_eval_nearest_args* a, void* stream
 }
 
 extern "C" int mipsf_eval_stats(const mipsf_eval_stats_args* a, void* stream) {
-    EVAL_ARGS(a, mipsf_eval_stats_args, "mipsf_eval_stats");
+    MIPSF_ARGS(a, mipsf_eval_stats_args, "mipsf_eval_stats");
     MIPSF_REQUIRE(a->record && a->workspace && (a->d2 || a->n == 0), "mipsf_eval_stats: null pointer");
     MIPSF_REQUIRE(((uintptr_t)a->workspace & 15u) == 0, "mipsf_eval_stats: workspace not 16-byte aligned");
     MIPSF_REQUIRE(a->threshold >= 0.0 && a->threshold < INFINITY, "mipsf_eval_stats: threshold %g", a->threshold);

@@ -194,8 +194,6 @@ __global__ void label_round_end_kernel(uint32_t* counts) {
     }
 }
 
-inline uint32_t blocks_for(uint32_t n) { return (n + TPB - 1) / TPB; }
-
 int points_check(const mipsf_fuse_points& P, const char* who) {
     if (P.points) return 0;
     MIPSF_REQUIRE(P.ticks[0] && P.ticks[1] && P.ticks[2], "%s: neither a point list nor tick arrays", who);
@@ -219,22 +217,17 @@ int camera_check(const mipsf_fuse_camera& c, const char* who) {
 
 using namespace mipsf;
 
-#define FUSE_ARGS(a, type, who)                                                                                              \
-    MIPSF_REQUIRE((a) != nullptr, who ": null argument block");                                                              \
-    MIPSF_REQUIRE((a)->struct_size == sizeof(type), #type ": struct_size %u, this library expects %u", (a)->struct_size, \
-                  (unsigned)sizeof(type))
-
 extern "C" int mipsf_fuse_visibility(const mipsf_fuse_visibility_args* a, void* stream) {
-    FUSE_ARGS(a, mipsf_fuse_visibility_args, "mipsf_fuse_visibility");
+    MIPSF_ARGS(a, mipsf_fuse_visibility_args, "mipsf_fuse_visibility");
     if (a->pts.n == 0) return 0;
     if (points_check(a->pts, "mipsf_fuse_visibility") || camera_check(a->cam, "mipsf_fuse_visibility")) return 1;
     MIPSF_REQUIRE(a->seen != nullptr, "mipsf_fuse_visibility: null output");
-    hipLaunchKernelGGL(fuse_visibility_kernel, dim3(blocks_for(a->pts.n)), dim3(TPB), 0, (hipStream_t)stream, a->pts, a->cam, a->seen);
+    hipLaunchKernelGGL(fuse_visibility_kernel, dim3(blocks_for(a->pts.n, TPB)), dim3(TPB), 0, (hipStream_t)stream, a->pts, a->cam, a->seen);
     return check_launch("fuse_visibility");
 }
 
 extern "C" int mipsf_fuse_local_points(const mipsf_fuse_local_args* a, void* stream) {
-    FUSE_ARGS(a, mipsf_fuse_local_args, "mipsf_fuse_local_points");
+    MIPSF_ARGS(a, mipsf_fuse_local_args, "mipsf_fuse_local_points");
     if (a->pts.n == 0) return 0;
     if (points_check(a->pts, "mipsf_fuse_local_points")) return 1;
     MIPSF_REQUIRE(a->out != nullptr, "mipsf_fuse_local_points: null output");
@@ -244,12 +237,12 @@ extern "C" int mipsf_fuse_local_points(const mipsf_fuse_local_args* a, void* str
         MIPSF_REQUIRE(a->div[d] != 0.0, "mipsf_fuse_local_points: zero extent on axis %d", d);
         L.sub[d] = a->sub[d], L.div[d] = a->div[d];
     }
-    hipLaunchKernelGGL(fuse_local_kernel, dim3(blocks_for(a->pts.n)), dim3(TPB), 0, (hipStream_t)stream, a->pts, L, a->out);
+    hipLaunchKernelGGL(fuse_local_kernel, dim3(blocks_for(a->pts.n, TPB)), dim3(TPB), 0, (hipStream_t)stream, a->pts, L, a->out);
     return check_launch("fuse_local_points");
 }
 
 extern "C" int mipsf_fuse_accumulate(const mipsf_fuse_accumulate_args* a, void* stream) {
-    FUSE_ARGS(a, mipsf_fuse_accumulate_args, "mipsf_fuse_accumulate");
+    MIPSF_ARGS(a, mipsf_fuse_accumulate_args, "mipsf_fuse_accumulate");
     if (a->pts.n == 0) return 0;
     if (points_check(a->pts, "mipsf_fuse_accumulate") || camera_check(a->cam, "mipsf_fuse_accumulate")) return 1;
     MIPSF_REQUIRE(a->channels == 1 || a->channels == 3, "mipsf_fuse_accumulate: %u channels (1 or 3)", a->channels);
@@ -269,33 +262,33 @@ extern "C" int mipsf_fuse_accumulate(const mipsf_fuse_accumulate_args* a, void* 
     for (int i = 0; i < 9; ++i) A.obb_axes[i] = a->obb_axes[i];
     A.sigma = a->sigma, A.gauss_k = a->gauss_k;
     A.num = a->num, A.den = a->den, A.flags = a->flags;
-    hipLaunchKernelGGL(fuse_accumulate_kernel, dim3(blocks_for(a->pts.n)), dim3(TPB), 0, (hipStream_t)stream, a->pts, a->cam, A);
+    hipLaunchKernelGGL(fuse_accumulate_kernel, dim3(blocks_for(a->pts.n, TPB)), dim3(TPB), 0, (hipStream_t)stream, a->pts, a->cam, A);
     return check_launch("fuse_accumulate");
 }
 
 extern "C" int mipsf_fuse_finalize(const mipsf_fuse_finalize_args* a, void* stream) {
-    FUSE_ARGS(a, mipsf_fuse_finalize_args, "mipsf_fuse_finalize");
+    MIPSF_ARGS(a, mipsf_fuse_finalize_args, "mipsf_fuse_finalize");
     if (a->n == 0) return 0;
     MIPSF_REQUIRE(a->num && a->den && (a->out || a->volume), "mipsf_fuse_finalize: null pointer");
     MIPSF_REQUIRE(a->channels == 1 || (a->channels == 3 && !a->volume), "mipsf_fuse_finalize: %u channels (1, or 3 without a volume)",
                   a->channels);
-    hipLaunchKernelGGL(fuse_finalize_kernel, dim3(blocks_for(a->n)), dim3(TPB), 0, (hipStream_t)stream, a->n, a->channels, a->num, a->den,
+    hipLaunchKernelGGL(fuse_finalize_kernel, dim3(blocks_for(a->n, TPB)), dim3(TPB), 0, (hipStream_t)stream, a->n, a->channels, a->num, a->den,
                        a->flags, a->out, a->volume);
     return check_launch("fuse_finalize");
 }
 
 extern "C" int mipsf_fuse_label_components(const mipsf_fuse_label_args* a, void* stream) {
-    FUSE_ARGS(a, mipsf_fuse_label_args, "mipsf_fuse_label_components");
+    MIPSF_ARGS(a, mipsf_fuse_label_args, "mipsf_fuse_label_components");
     MIPSF_REQUIRE(a->counts != nullptr, "mipsf_fuse_label_components: null counts");
     MIPSF_REQUIRE(a->F < (1u << 31) && a->E < (1u << 31), "mipsf_fuse_label_components: 2^31 items or pairs, or more");
     MIPSF_REQUIRE(a->F == 0 || a->labels != nullptr, "mipsf_fuse_label_components: null labels");
     MIPSF_REQUIRE(a->E == 0 || a->pairs != nullptr, "mipsf_fuse_label_components: null pairs");
     const hipStream_t s = (hipStream_t)stream;
-    if (!a->resume) hipLaunchKernelGGL(label_init_kernel, dim3(blocks_for(a->F > 4 ? a->F : 4)), dim3(TPB), 0, s, a->labels, a->F, a->counts);
+    if (!a->resume) hipLaunchKernelGGL(label_init_kernel, dim3(blocks_for(a->F > 4 ? a->F : 4, TPB)), dim3(TPB), 0, s, a->labels, a->F, a->counts);
     if (a->F && a->E)
         for (uint32_t r = 0; r < a->max_rounds; ++r) {
-            hipLaunchKernelGGL(label_hook_kernel, dim3(blocks_for(a->E)), dim3(TPB), 0, s, a->pairs, a->E, a->F, a->labels, a->counts);
-            hipLaunchKernelGGL(label_jump_kernel, dim3(blocks_for(a->F)), dim3(TPB), 0, s, a->labels, a->F);
+            hipLaunchKernelGGL(label_hook_kernel, dim3(blocks_for(a->E, TPB)), dim3(TPB), 0, s, a->pairs, a->E, a->F, a->labels, a->counts);
+            hipLaunchKernelGGL(label_jump_kernel, dim3(blocks_for(a->F, TPB)), dim3(TPB), 0, s, a->labels, a->F);
             hipLaunchKernelGGL(label_round_end_kernel, dim3(1), dim3(64), 0, s, a->counts);
         }
     return check_launch("fuse_label_components");

@@ -8,6 +8,7 @@
 // order of the points inside a cell (the scatter's integer atomics decide it) reaches a result.  Sums that feed a result are
 // added in a fixed order: lane -> wave (cross-lane moves) -> block partials in a buffer -> one finishing wave.  The library is
 // built with -ffp-contract=off.
+#include "block_dev.h"
 #include "icp_grid.h"
 #include "../../include/mipsf_icp.h"
 
@@ -17,87 +18,29 @@ namespace {
 constexpr int TPB = GRID_TPB;
 constexpr int WAVES = TPB / MIPSF_WAVE;
 constexpr int SCAN_TILE = GRID_SCAN_TILE; // entries one block scans
+static_assert(SCAN_TILE == TPB * SCAN_ITEMS, "the grid's layout counts the tiles of block_dev.h's scan");
 constexpr int KNN = MIPSF_ICP_KNN;
 constexpr int NSUM = 29;                 // 21 (upper triangle of J^T J) + 6 (J^T r) + pairs + sum of squared distances
 constexpr int NSUM_PAD = 32;
 
 // ------------------------------------------------------------------------------------------------ exclusive scan of uint32
-__device__ __forceinline__ uint32_t wave_excl_scan(uint32_t v, uint32_t& total) {
-    const int lane = threadIdx.x & 63;
-    uint32_t inc = v;
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-        const uint32_t t = __shfl_up(inc, o, 64);
-        if (lane >= o) inc += t;
-    }
-    total = __shfl(inc, 63, 64);
-    return inc - v;
-}
-
-// over the TPB threads of a block; sm holds WAVES words
-__device__ __forceinline__ uint32_t block_excl_scan(uint32_t v, uint32_t& total, uint32_t* sm) {
-    uint32_t wt;
-    const uint32_t ex = wave_excl_scan(v, wt);
-    const int w = threadIdx.x >> 6;
-    if ((threadIdx.x & 63) == 0) sm[w] = wt;
-    __syncthreads();
-    uint32_t base = 0;
-    total = 0;
-#pragma unroll
-    for (int i = 0; i < WAVES; ++i) {
-        if (i < w) base += sm[i];
-        total += sm[i];
-    }
-    __syncthreads();
-    return base + ex;
-}
-
 __global__ void __launch_bounds__(TPB) scan_sums_kernel(const uint32_t* in, uint32_t n, uint32_t* bsum) {
     __shared__ uint32_t sm[WAVES];
-    const uint64_t base = (uint64_t)blockIdx.x * SCAN_TILE + threadIdx.x * 4;
-    uint32_t s = 0;
-#pragma unroll
-    for (int k = 0; k < 4; ++k)
-        if (base + k < n) s += in[base + k];
-    uint32_t total;
-    block_excl_scan(s, total, sm);
+    const uint32_t total = scan_tile_sum<WAVES>(in, n, sm);
     if (threadIdx.x == 0) bsum[blockIdx.x] = total;
 }
 
 // one block: bsum[0..nb) becomes its exclusive scan, *total_out the sum
 __global__ void __launch_bounds__(TPB) scan_top_kernel(uint32_t* bsum, uint32_t nb, uint32_t* total_out) {
     __shared__ uint32_t sm[WAVES];
-    const uint32_t chunk = (nb + TPB - 1) / TPB;
-    const uint32_t lo = min(threadIdx.x * chunk, nb), hi = min(lo + chunk, nb);
-    uint32_t s = 0;
-    for (uint32_t i = lo; i < hi; ++i) s += bsum[i];
-    uint32_t total;
-    uint32_t run = block_excl_scan(s, total, sm);
-    for (uint32_t i = lo; i < hi; ++i) {
-        const uint32_t t = bsum[i];
-        bsum[i] = run;
-        run += t;
-    }
+    const uint32_t total = scan_top<WAVES>(bsum, nb, sm);
     if (threadIdx.x == 0 && total_out) *total_out = total;
 }
 
 // out may be in
 __global__ void __launch_bounds__(TPB) scan_apply_kernel(const uint32_t* in, uint32_t n, const uint32_t* bsum, uint32_t* out) {
     __shared__ uint32_t sm[WAVES];
-    const uint64_t base = (uint64_t)blockIdx.x * SCAN_TILE + threadIdx.x * 4;
-    uint32_t v[4], s = 0;
-#pragma unroll
-    for (int k = 0; k < 4; ++k) {
-        v[k] = base + k < n ? in[base + k] : 0u;
-        s += v[k];
-    }
-    uint32_t total;
-    uint32_t run = block_excl_scan(s, total, sm) + bsum[blockIdx.x];
-#pragma unroll
-    for (int k = 0; k < 4; ++k) {
-        if (base + k < n) out[base + k] = run;
-        run += v[k];
-    }
+    scan_apply<WAVES, false>(in, n, bsum, out, sm);
 }
 
 // exclusive scan of in[0..n) into out (may alias), the sum into *total_out (optional); bsum: blocks_for(n, SCAN_TILE) words
@@ -146,6 +89,15 @@ MIPSF_SINGLE_FP32 __global__ void __launch_bounds__(TPB) cloud_emit_kernel(Cloud
 }
 
 // ------------------------------------------------------------------------------------------------ grid (its layout: icp_grid.h)
+// a box {min x y z, max x y z} over the wave, in every lane
+__device__ __forceinline__ void box_wave_reduce(float v[6]) {
+#pragma unroll
+    for (int d = 0; d < 3; ++d) {
+        v[d] = wave_reduce(v[d], [](float a, float b) { return fminf(a, b); });
+        v[3 + d] = wave_reduce(v[3 + d], [](float a, float b) { return fmaxf(a, b); });
+    }
+}
+
 MIPSF_SINGLE_FP32 __global__ void __launch_bounds__(TPB) bbox_partial_kernel(const float* __restrict__ pts, uint32_t n,
                                                                              float* __restrict__ part) {
     __shared__ float sm[WAVES][6];
@@ -155,13 +107,7 @@ MIPSF_SINGLE_FP32 __global__ void __launch_bounds__(TPB) bbox_partial_kernel(con
 #pragma unroll
         for (int d = 0; d < 3; ++d) v[d] = v[3 + d] = pts[(size_t)i * 3 + d];
     }
-#pragma unroll
-    for (int d = 0; d < 3; ++d)
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) {
-            v[d] = fminf(v[d], __shfl_xor(v[d], o, 64));
-            v[3 + d] = fmaxf(v[3 + d], __shfl_xor(v[3 + d], o, 64));
-        }
+    box_wave_reduce(v);
     if ((threadIdx.x & 63) == 0)
 #pragma unroll
         for (int d = 0; d < 6; ++d) sm[threadIdx.x >> 6][d] = v[d];
@@ -183,13 +129,7 @@ MIPSF_SINGLE_FP32 __global__ void __launch_bounds__(MIPSF_WAVE) bbox_finish_kern
             v[d] = fminf(v[d], part[(size_t)b * 6 + d]);
             v[3 + d] = fmaxf(v[3 + d], part[(size_t)b * 6 + 3 + d]);
         }
-#pragma unroll
-    for (int d = 0; d < 3; ++d)
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) {
-            v[d] = fminf(v[d], __shfl_xor(v[d], o, 64));
-            v[3 + d] = fmaxf(v[3 + d], __shfl_xor(v[3 + d], o, 64));
-        }
+    box_wave_reduce(v);
     if (threadIdx.x != 0) return;
     double ext[3] = {0.0, 0.0, 0.0};
     if (n > 0)
@@ -653,7 +593,7 @@ RegLayout reg_layout(uint32_t n_source) {
     L.state = 0;
     L.P = 256;
     L.partial = align16(L.P + (uint64_t)(n_source ? n_source : 1) * 3 * sizeof(double));
-    L.bytes = L.partial + (uint64_t)blocks_for(n_source ? n_source : 1) * NSUM_PAD * sizeof(double);
+    L.bytes = L.partial + (uint64_t)blocks_for(n_source ? n_source : 1, TPB) * NSUM_PAD * sizeof(double);
     return L;
 }
 static_assert(sizeof(IcpState) <= 256, "IcpState");
@@ -662,11 +602,6 @@ static_assert(sizeof(IcpState) <= 256, "IcpState");
 }  // namespace mipsf
 
 using namespace mipsf;
-
-#define ICP_ARGS(a, type, name)                                                                                          \
-    MIPSF_REQUIRE((a) != nullptr, name ": null argument block");                                                         \
-    MIPSF_REQUIRE((a)->struct_size == sizeof(type), #type ": struct_size %u, this library expects %u", (a)->struct_size, \
-                  (unsigned)sizeof(type))
 
 extern "C" uint64_t mipsf_icp_workspace_bytes(int which, uint32_t n, uint32_t cells) {
     if (n > MIPSF_ICP_MAX_POINTS) return 0;
@@ -684,7 +619,7 @@ extern "C" uint64_t mipsf_icp_workspace_bytes(int which, uint32_t n, uint32_t ce
 }
 
 extern "C" int mipsf_icp_cloud(const mipsf_icp_cloud_args* a, void* stream) {
-    ICP_ARGS(a, mipsf_icp_cloud_args, "mipsf_icp_cloud");
+    MIPSF_ARGS(a, mipsf_icp_cloud_args, "mipsf_icp_cloud");
     MIPSF_REQUIRE(a->count != nullptr, "mipsf_icp_cloud: null count");
     MIPSF_REQUIRE(a->n <= MIPSF_ICP_MAX_POINTS, "mipsf_icp_cloud: %u rows, at most %u", a->n, MIPSF_ICP_MAX_POINTS);
     hipStream_t s = (hipStream_t)stream;
@@ -702,14 +637,14 @@ extern "C" int mipsf_icp_cloud(const mipsf_icp_cloud_args* a, void* stream) {
     uint32_t* flags = (uint32_t*)a->workspace;
     uint32_t* bsum = (uint32_t*)((char*)a->workspace + align16((uint64_t)a->n * 4));
     const CloudCfg c = {a->rows, a->owner, a->poses, a->n, a->k, a->rows_per_owner};
-    hipLaunchKernelGGL(cloud_flag_kernel, dim3(blocks_for(a->n)), dim3(TPB), 0, s, c, flags);
+    hipLaunchKernelGGL(cloud_flag_kernel, dim3(blocks_for(a->n, TPB)), dim3(TPB), 0, s, c, flags);
     enqueue_scan(flags, a->n, flags, bsum, a->count, s);
-    hipLaunchKernelGGL(cloud_emit_kernel, dim3(blocks_for(a->n)), dim3(TPB), 0, s, c, (const uint32_t*)flags, a->points);
+    hipLaunchKernelGGL(cloud_emit_kernel, dim3(blocks_for(a->n, TPB)), dim3(TPB), 0, s, c, (const uint32_t*)flags, a->points);
     return check_launch("icp_cloud");
 }
 
 extern "C" int mipsf_icp_bin(const mipsf_icp_bin_args* a, void* stream) {
-    ICP_ARGS(a, mipsf_icp_bin_args, "mipsf_icp_bin");
+    MIPSF_ARGS(a, mipsf_icp_bin_args, "mipsf_icp_bin");
     MIPSF_REQUIRE(a->grid != nullptr && (a->points != nullptr || a->n == 0), "mipsf_icp_bin: null pointer");
     MIPSF_REQUIRE(((uintptr_t)a->grid & 15u) == 0, "mipsf_icp_bin: grid not 16-byte aligned");
     MIPSF_REQUIRE(a->n <= MIPSF_ICP_MAX_POINTS, "mipsf_icp_bin: %u points, at most %u", a->n, MIPSF_ICP_MAX_POINTS);
@@ -725,7 +660,7 @@ extern "C" int mipsf_icp_bin(const mipsf_icp_bin_args* a, void* stream) {
     uint32_t* cnt = (uint32_t*)(b + L.cnt);
     uint32_t* bsum = (uint32_t*)(b + L.bsum);
     float4* sorted = (float4*)(b + L.sorted);
-    const uint32_t nb = a->n ? blocks_for(a->n) : 0;
+    const uint32_t nb = a->n ? blocks_for(a->n, TPB) : 0;
     if (hipMemsetAsync(cnt, 0, ((size_t)a->max_cells + 1) * 4, s) != hipSuccess) {
         set_error("mipsf_icp_bin: memset failed");
         return 1;
@@ -739,19 +674,19 @@ extern "C" int mipsf_icp_bin(const mipsf_icp_bin_args* a, void* stream) {
 }
 
 extern "C" int mipsf_icp_nearest(const mipsf_icp_nearest_args* a, void* stream) {
-    ICP_ARGS(a, mipsf_icp_nearest_args, "mipsf_icp_nearest");
+    MIPSF_ARGS(a, mipsf_icp_nearest_args, "mipsf_icp_nearest");
     if (a->n_source == 0) return 0;
     MIPSF_REQUIRE(a->source && a->grid && a->partner, "mipsf_icp_nearest: null pointer");
     MIPSF_REQUIRE(a->n_source <= MIPSF_ICP_MAX_POINTS && a->n_target <= MIPSF_ICP_MAX_POINTS, "mipsf_icp_nearest: too many points");
     MIPSF_REQUIRE(a->max_cells >= 1 && a->max_cells <= MIPSF_ICP_MAX_CELLS, "mipsf_icp_nearest: max_cells %u", a->max_cells);
     MIPSF_REQUIRE(a->max_dist >= 0.0 && a->max_dist < INFINITY, "mipsf_icp_nearest: max_dist %g", a->max_dist);
-    hipLaunchKernelGGL(nearest_kernel, dim3(blocks_for(a->n_source)), dim3(TPB), 0, (hipStream_t)stream, a->source, a->n_source, a->n_target,
+    hipLaunchKernelGGL(nearest_kernel, dim3(blocks_for(a->n_source, TPB)), dim3(TPB), 0, (hipStream_t)stream, a->source, a->n_source, a->n_target,
                        grid_view(a->grid, a->n_target, a->max_cells), a->max_dist * a->max_dist, a->partner, a->d2);
     return check_launch("icp_nearest");
 }
 
 extern "C" int mipsf_icp_normals(const mipsf_icp_normals_args* a, void* stream) {
-    ICP_ARGS(a, mipsf_icp_normals_args, "mipsf_icp_normals");
+    MIPSF_ARGS(a, mipsf_icp_normals_args, "mipsf_icp_normals");
     if (a->n == 0) return 0;
     MIPSF_REQUIRE(a->points && a->grid && a->normals, "mipsf_icp_normals: null pointer");
     MIPSF_REQUIRE(a->n <= MIPSF_ICP_MAX_POINTS, "mipsf_icp_normals: too many points");
@@ -762,7 +697,7 @@ extern "C" int mipsf_icp_normals(const mipsf_icp_normals_args* a, void* stream) 
 }
 
 extern "C" int mipsf_icp_register(const mipsf_icp_register_args* a, void* stream) {
-    ICP_ARGS(a, mipsf_icp_register_args, "mipsf_icp_register");
+    MIPSF_ARGS(a, mipsf_icp_register_args, "mipsf_icp_register");
     MIPSF_REQUIRE(a->result && a->workspace && a->grid, "mipsf_icp_register: null pointer");
     MIPSF_REQUIRE((a->source || a->n_source == 0) && (a->target_normals || a->n_target == 0), "mipsf_icp_register: null pointer");
     MIPSF_REQUIRE(((uintptr_t)a->workspace & 15u) == 0, "mipsf_icp_register: workspace not 16-byte aligned");
@@ -777,8 +712,8 @@ extern "C" int mipsf_icp_register(const mipsf_icp_register_args* a, void* stream
     double* P = (double*)(w + L.P);
     double* partial = (double*)(w + L.partial);
     const Grid g = grid_view(a->grid, a->n_target, a->max_cells);
-    const uint32_t nb = a->n_source ? blocks_for(a->n_source) : 0;
-    hipLaunchKernelGGL(icp_init_kernel, dim3(blocks_for(a->n_source ? (uint64_t)a->n_source * 3 : 1)), dim3(TPB), 0, s, a->source,
+    const uint32_t nb = a->n_source ? blocks_for(a->n_source, TPB) : 0;
+    hipLaunchKernelGGL(icp_init_kernel, dim3(blocks_for(a->n_source ? (uint64_t)a->n_source * 3 : 1, TPB)), dim3(TPB), 0, s, a->source,
                        a->n_source * 3, P, st, a->result);
     for (uint32_t k = 0; k <= a->max_iteration; ++k) {
         if (nb)

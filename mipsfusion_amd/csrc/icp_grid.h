@@ -9,10 +9,7 @@
 namespace mipsf {
 
 constexpr int GRID_TPB = 256;                 // threads of the grid's kernels; the box partials are per block of this size
-constexpr int GRID_SCAN_TILE = GRID_TPB * 4;  // entries one block of the cell scan takes
-
-inline uint32_t blocks_for(uint64_t n, uint32_t per = GRID_TPB) { return (uint32_t)((n + per - 1) / per); }
-inline uint64_t align16(uint64_t v) { return (v + 15u) & ~(uint64_t)15u; }
+constexpr int GRID_SCAN_TILE = GRID_TPB * 4;  // entries one block of the cell scan takes (block_dev.h: SCAN_ITEMS a thread)
 
 struct GridHdr {
     double origin[3];
@@ -31,7 +28,7 @@ inline GridLayout grid_layout(uint32_t n, uint32_t cells) {
     GridLayout L;
     L.hdr = 0;
     L.bbox = 128;
-    L.start = align16(L.bbox + (uint64_t)blocks_for(n ? n : 1) * 6 * sizeof(float));
+    L.start = align16(L.bbox + (uint64_t)blocks_for(n ? n : 1, GRID_TPB) * 6 * sizeof(float));
     L.cnt = align16(L.start + ((uint64_t)cells + 1) * 4);
     L.bsum = align16(L.cnt + ((uint64_t)cells + 1) * 4);
     L.sorted = align16(L.bsum + (uint64_t)blocks_for((uint64_t)cells + 1, GRID_SCAN_TILE) * 4);

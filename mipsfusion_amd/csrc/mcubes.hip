@@ -1,7 +1,7 @@
 // Mesh extraction on the device: marching cubes over the dual grid of an SDF volume with the upstream extractor's semantics
 // (include/mipsf_mesh.h).  count = classify + reduce + scan, emit, weld.  The order of the soup is defined by
 // scans only (no atomics); the weld uses atomicMin / atomicCAS on a hash table, whose fixed point does not depend on scheduling.
-#include "common.h"
+#include "block_dev.h"
 #include "../../include/mipsf_mesh.h"
 #include "mcubes_tables.h"
 
@@ -20,6 +20,7 @@ constexpr int VX = BX + 2, VY = BY + 2, VZ = BZ + 2;
 constexpr int DX = BX + 1, DY = BY + 1, DZ = BZ + 1;
 constexpr uint32_t ITEMS = 16;                  // consecutive elements per thread of the scan family
 constexpr uint32_t CHUNK = MIPSF_MCUBES_BLOCK_CELLS;
+constexpr int WAVES = 256 / MIPSF_WAVE;         // of a workgroup of the scan family
 static_assert(CHUNK == 256 * ITEMS, "a block of the offset table is one workgroup of the scan family");
 
 // the eight voxels of a dual value in the order they are summed
@@ -103,31 +104,7 @@ MIPSF_SINGLE_FP32 __global__ __launch_bounds__(256) void mcubes_classify_kernel(
     }
 }
 
-// ---- the scan family: a workgroup owns CHUNK consecutive elements, a thread ITEMS consecutive ones
-__device__ __forceinline__ uint32_t wave_incl_scan(uint32_t v) {
-    const int lane = threadIdx.x & 63;
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-        const uint32_t u = __shfl_up(v, o, 64);
-        if (lane >= o) v += u;
-    }
-    return v;
-}
-
-// exclusive prefix of `mine` over the 256 threads of the workgroup; *total = the workgroup's sum
-__device__ __forceinline__ uint32_t block_excl_scan(uint32_t mine, uint32_t* total) {
-    __shared__ uint32_t wsum[4];
-    const uint32_t incl = wave_incl_scan(mine);
-    const int wave = threadIdx.x >> 6;
-    __syncthreads();
-    if ((threadIdx.x & 63) == 63) wsum[wave] = incl;
-    __syncthreads();
-    uint32_t base = 0;
-    for (int w = 0; w < wave; ++w) base += wsum[w];
-    *total = wsum[0] + wsum[1] + wsum[2] + wsum[3];
-    return base + incl - mine;
-}
-
+// ---- the scan family: a workgroup owns CHUNK consecutive elements, a thread ITEMS consecutive ones; the scans are block_dev.h's
 // the case bytes of a thread's ITEMS cells (0 beyond the end)
 __device__ __forceinline__ void load_cases(const uint8_t* __restrict__ cases, uint32_t n, uint32_t first, uint8_t out[ITEMS]) {
     if (first + ITEMS <= n && (first & 15u) == 0) {
@@ -143,13 +120,13 @@ __device__ __forceinline__ void load_cases(const uint8_t* __restrict__ cases, ui
 
 __global__ __launch_bounds__(256) void mcubes_reduce_kernel(const uint8_t* __restrict__ cases, uint32_t n,
                                                             uint32_t* __restrict__ block_sums) {
+    __shared__ uint32_t wsum[WAVES];
     uint8_t cs[ITEMS];
     load_cases(cases, n, blockIdx.x * CHUNK + threadIdx.x * ITEMS, cs);
     uint32_t mine = 0;
 #pragma unroll
     for (uint32_t q = 0; q < ITEMS; ++q) mine += k_ntri[cs[q]];
-    uint32_t total;
-    block_excl_scan(mine, &total);
+    const uint32_t total = block_reduce<WAVES>(mine, wsum, Add());
     if (threadIdx.x == 0) block_sums[blockIdx.x] = total;
 }
 
@@ -198,6 +175,7 @@ MIPSF_SINGLE_FP32 __global__ __launch_bounds__(256) void mcubes_emit_kernel(cons
                                                                            const uint32_t* __restrict__ block_offsets,
                                                                            float* __restrict__ soup, int32_t* __restrict__ cell_ids,
                                                                            uint32_t capacity) {
+    __shared__ uint32_t wsum[WAVES];
     const uint32_t n = (uint32_t)X * Y * Z;
     const uint32_t first = blockIdx.x * CHUNK + threadIdx.x * ITEMS;
     uint8_t cs[ITEMS];
@@ -205,8 +183,7 @@ MIPSF_SINGLE_FP32 __global__ __launch_bounds__(256) void mcubes_emit_kernel(cons
     uint32_t mine = 0;
 #pragma unroll
     for (uint32_t q = 0; q < ITEMS; ++q) mine += k_ntri[cs[q]];
-    uint32_t total;
-    uint32_t off = block_offsets[blockIdx.x] + block_excl_scan(mine, &total);
+    uint32_t off = block_offsets[blockIdx.x] + block_excl_scan<WAVES>(mine, wsum);
     if (mine == 0) return;
     for (uint32_t q = 0; q < ITEMS; ++q) {
         const uint32_t code = cs[q];
@@ -370,12 +347,12 @@ __global__ __launch_bounds__(256) void weld_root_kernel(uint32_t n, WeldTable tb
 
 __global__ __launch_bounds__(256) void weld_reduce_kernel(const uint32_t* __restrict__ root, uint32_t n,
                                                           uint32_t* __restrict__ block_sums) {
+    __shared__ uint32_t wsum[WAVES];
     const uint32_t first = blockIdx.x * CHUNK + threadIdx.x * ITEMS;
     uint32_t mine = 0;
     for (uint32_t q = 0; q < ITEMS; ++q)
         if (first + q < n && root[first + q] == first + q) ++mine;
-    uint32_t total;
-    block_excl_scan(mine, &total);
+    const uint32_t total = block_reduce<WAVES>(mine, wsum, Add());
     if (threadIdx.x == 0) block_sums[blockIdx.x] = total;
 }
 
@@ -384,12 +361,12 @@ __global__ __launch_bounds__(256) void weld_compact_kernel(const float* __restri
                                                            const uint32_t* __restrict__ block_offsets,
                                                            uint32_t* __restrict__ new_id, float* __restrict__ vertices,
                                                            uint32_t* __restrict__ counts) {
+    __shared__ uint32_t wsum[WAVES];
     const uint32_t first = blockIdx.x * CHUNK + threadIdx.x * ITEMS;
     uint32_t mine = 0;
     for (uint32_t q = 0; q < ITEMS; ++q)
         if (first + q < n && root[first + q] == first + q) ++mine;
-    uint32_t total;
-    uint32_t off = block_offsets[blockIdx.x] + block_excl_scan(mine, &total);
+    uint32_t off = block_offsets[blockIdx.x] + block_excl_scan<WAVES>(mine, wsum);
     for (uint32_t q = 0; q < ITEMS; ++q) {
         const uint32_t v = first + q;
         if (v < n && root[v] == v) {
@@ -440,9 +417,7 @@ uint64_t mcubes_weld_words(uint32_t T) {
 using namespace mipsf;
 
 static int mcubes_check(const mipsf_mcubes_args* a, const char* who) {
-    MIPSF_REQUIRE(a != nullptr, "%s: null argument block", who);
-    MIPSF_REQUIRE(a->struct_size == sizeof(mipsf_mcubes_args), "mipsf_mcubes_args: struct_size %u, this library expects %u",
-                  a->struct_size, (unsigned)sizeof(mipsf_mcubes_args));
+    MIPSF_ARGS(a, mipsf_mcubes_args, who);
     MIPSF_REQUIRE(a->X >= 1 && a->Y >= 1 && a->Z >= 1 && mcubes_offset_words(a->X, a->Y, a->Z) != 0,
                   "%s: volume %u x %u x %u is empty or has 2^31 cells or more", who, a->X, a->Y, a->Z);
     MIPSF_REQUIRE(a->volume && a->cases && a->block_offsets, "%s: null pointer", who);
@@ -475,9 +450,7 @@ extern "C" int mipsf_mcubes_emit(const mipsf_mcubes_args* a, void* stream) {
 }
 
 extern "C" int mipsf_mcubes_weld(const mipsf_mcubes_weld_args* a, void* stream) {
-    MIPSF_REQUIRE(a != nullptr, "mipsf_mcubes_weld: null argument block");
-    MIPSF_REQUIRE(a->struct_size == sizeof(mipsf_mcubes_weld_args), "mipsf_mcubes_weld_args: struct_size %u, this library expects %u",
-                  a->struct_size, (unsigned)sizeof(mipsf_mcubes_weld_args));
+    MIPSF_ARGS(a, mipsf_mcubes_weld_args, "mipsf_mcubes_weld");
     MIPSF_REQUIRE(a->counts != nullptr && a->scratch != nullptr, "mipsf_mcubes_weld: null pointer");
     MIPSF_REQUIRE(((uintptr_t)a->scratch & 7u) == 0, "mipsf_mcubes_weld: scratch must be 8-byte aligned");
     const uint64_t slots = mcubes_weld_slots(a->T);

@@ -3,7 +3,7 @@
 // edges of a block added in ascending index, a dense float64 Cholesky and two triangular solves by the workgroup (packed lower
 // triangle, in LDS up to MIPSF_POSEGRAPH_LDS_NODES nodes, in the workspace above).  A latency kernel: the barriers between the
 // factorisation's columns are its cost.  tests/posegraph_cpu.py is the restatement every formula here follows line by line.
-#include "common.h"
+#include "block_dev.h"
 
 #include <math.h>
 
@@ -263,20 +263,12 @@ __device__ double edge_residual(const double* P, const double* Xa, const double*
     return sum;
 }
 
-__device__ __forceinline__ double block_sum(double v, double* red) {
-    v = wave_sum_d(v);
-    __syncthreads();
-    if ((threadIdx.x & (MIPSF_WAVE - 1)) == 0) red[threadIdx.x / MIPSF_WAVE] = v;
-    __syncthreads();
-    return ((red[0] + red[1]) + red[2]) + red[3];
-}
-
 __device__ __forceinline__ int tri(int i) { return i * (i + 1) / 2; }
 
 __global__ __launch_bounds__(PG_TPB) void posegraph_kernel(const PgCfg c) {
     __shared__ double s_tri[PG_LDS_TRI];
     __shared__ double s_b[PG_MAX_N], s_x[PG_MAX_N], s_dg[PG_MAX_N];
-    __shared__ double s_red[PG_TPB / MIPSF_WAVE];
+    __shared__ double s_red[PG_WAVES];
     __shared__ int s_flag;
     __shared__ uint8_t s_ea[PG_MAX_EDGES], s_eb[PG_MAX_EDGES];
 
@@ -307,7 +299,7 @@ __global__ __launch_bounds__(PG_TPB) void posegraph_kernel(const PgCfg c) {
         double v = 0.0;
         for (int e = tid; e < E; e += PG_TPB)
             v += edge_residual(P + e * 12, X + s_ea[e] * 12, X + s_eb[e] * 12, c.weights[e], record ? rec + (size_t)e * PG_EDGE_DOUBLES : nullptr);
-        return block_sum(v, s_red);
+        return block_reduce<PG_WAVES>(v, s_red, Add());
     };
     // J^T J without its diagonal (-> A), b = -J^T r (-> s_b, which the solve then consumes) and, with `first`, the clamped diagonal
     // (-> s_dg); one 6x6 block per lane, the edges of a block in ascending index
@@ -471,7 +463,7 @@ __global__ __launch_bounds__(PG_TPB) void posegraph_kernel(const PgCfg c) {
 #pragma unroll
                     for (int k = 0; k < 6; ++k) v += u[k] * (2.0 * r[k] + u[k]);
                 }
-                const double den = -block_sum(v, s_red);
+                const double den = -block_reduce<PG_WAVES>(v, s_red, Add());
                 const double quality = (last - loss) / den;
                 if (quality > 0.5) {
                     radius *= 2.0, down = 0.5;
@@ -521,9 +513,7 @@ extern "C" uint64_t mipsf_posegraph_workspace_bytes(uint32_t n_nodes, uint32_t n
 }
 
 extern "C" int mipsf_posegraph_optimize(const mipsf_posegraph_args* a, void* stream) {
-    MIPSF_REQUIRE(a != nullptr, "mipsf_posegraph_optimize: null argument block");
-    MIPSF_REQUIRE(a->struct_size == sizeof(mipsf_posegraph_args), "mipsf_posegraph_args: struct_size %u, this library expects %u", a->struct_size,
-                  (unsigned)sizeof(mipsf_posegraph_args));
+    MIPSF_ARGS(a, mipsf_posegraph_args, "mipsf_posegraph_optimize");
     MIPSF_REQUIRE(a->n_nodes >= 2 && a->n_nodes <= MIPSF_POSEGRAPH_MAX_NODES, "mipsf_posegraph_optimize: %u nodes, accepted are 2 .. %u", a->n_nodes,
                   MIPSF_POSEGRAPH_MAX_NODES);
     MIPSF_REQUIRE(a->n_edges >= 1 && a->n_edges <= MIPSF_POSEGRAPH_MAX_EDGES, "mipsf_posegraph_optimize: %u edges, accepted are 1 .. %u", a->n_edges,

@@ -3,11 +3,11 @@
 // Co-SLAM evaluation, which renders with a host library.  DESIGN.md 4.18.
 //
 // Shape of the kernels: one (view, face) pair per lane counts the 8 x 8 tiles of the face's screen box; the counts become a
-// 64-bit prefix sum (the scheme of eval.hip); one wavefront takes one tile, one lane one pixel, finds its pair by binary search
-// in the sum, recomputes the face's cross products and tests its pixel by the header's float64 rule; the winner of a pixel is the
+// 64-bit prefix sum (block_dev.h's device-wide scan); one wavefront takes one tile, one lane one pixel, finds its pair by binary
+// search in the sum, recomputes the face's cross products and tests its pixel by the header's float64 rule; the winner of a pixel is the
 // integer minimum of (depth bits, face index), so the image is the same in any order of work.  The screen box is the only
 // arithmetic here that the header does not fix: it may be generous, it must never leave out a pixel the rule hits.
-#include "common.h"
+#include "block_dev.h"
 #include "../../include/mipsf_raster.h"
 
 namespace mipsf {
@@ -15,53 +15,12 @@ namespace {
 
 constexpr int TPB = 256;
 constexpr int WAVES = TPB / MIPSF_WAVE;
-constexpr int SCAN_TILE = TPB * 4;              // items one block scans
+constexpr int SCAN_TILE = TPB * SCAN_ITEMS;     // items one block scans
 constexpr uint32_t TILE = MIPSF_RASTER_TILE;
 constexpr uint32_t L1_MAX_BLOCKS = 256;         // partials per view
 constexpr uint64_t KEY_EMPTY = ~0ull;
 static_assert(TILE * TILE == MIPSF_WAVE, "one lane per pixel of a tile");
 static_assert(sizeof(mipsf_raster_l1_record) == 64, "l1 record");
-
-inline uint32_t blocks_for(uint64_t n, uint32_t per) { return (uint32_t)((n + per - 1) / per); }
-inline uint64_t align16(uint64_t v) { return (v + 15u) & ~(uint64_t)15u; }
-
-// ------------------------------------------------------------------------------------------------ sums and scans of uint64
-__device__ __forceinline__ uint64_t wave_sum_u64(uint64_t v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += (uint64_t)__shfl_xor((unsigned long long)v, o, 64);
-    return v;
-}
-
-// the sum over the TPB threads of a block, in every thread; sm holds WAVES words
-__device__ __forceinline__ uint64_t block_sum_u64(uint64_t v, uint64_t* sm) {
-    v = wave_sum_u64(v);
-    if ((threadIdx.x & 63) == 0) sm[threadIdx.x >> 6] = v;
-    __syncthreads();
-    uint64_t total = 0;
-#pragma unroll
-    for (int i = 0; i < WAVES; ++i) total += sm[i];
-    __syncthreads();
-    return total;
-}
-
-// exclusive scan over the TPB threads of a block; sm holds WAVES words
-__device__ __forceinline__ uint64_t block_excl_scan_u64(uint64_t v, uint64_t* sm) {
-    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-    uint64_t inc = v;
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-        const uint64_t t = (uint64_t)__shfl_up((unsigned long long)inc, o, 64);
-        if (lane >= o) inc += t;
-    }
-    if (lane == 63) sm[w] = inc;
-    __syncthreads();
-    uint64_t base = 0;
-#pragma unroll
-    for (int i = 0; i < WAVES; ++i)
-        if (i < w) base += sm[i];
-    __syncthreads();
-    return base + (inc - v);
-}
 
 // ------------------------------------------------------------------------------------------------ the face and its screen box
 struct Scene {
@@ -209,10 +168,10 @@ __global__ void __launch_bounds__(TPB) raster_clear_kernel(uint64_t* __restrict_
 MIPSF_SINGLE_FP32 __global__ void __launch_bounds__(TPB) raster_count_kernel(Scene s, uint32_t items, uint64_t* __restrict__ cum,
                                                                              uint64_t* __restrict__ tiles) {
     __shared__ uint64_t sm[WAVES];
-    const uint64_t base = (uint64_t)blockIdx.x * SCAN_TILE + threadIdx.x * 4;
+    const uint64_t base = (uint64_t)blockIdx.x * SCAN_TILE + threadIdx.x * SCAN_ITEMS;
     uint64_t sum = 0;
 #pragma unroll 1
-    for (int k = 0; k < 4; ++k)
+    for (int k = 0; k < SCAN_ITEMS; ++k)
         if (base + k < items) {
             const uint32_t item = (uint32_t)(base + k);
             Face face;
@@ -221,41 +180,20 @@ MIPSF_SINGLE_FP32 __global__ void __launch_bounds__(TPB) raster_count_kernel(Sce
             cum[item] = c;
             sum += c;
         }
-    sum = block_sum_u64(sum, sm);
+    sum = block_reduce<WAVES>(sum, sm, Add());
     if (threadIdx.x == 0) tiles[blockIdx.x] = sum;
 }
 
 // one block: tiles[0..nb) becomes its exclusive scan
 __global__ void __launch_bounds__(TPB) raster_scan_top_kernel(uint64_t* tiles, uint32_t nb) {
     __shared__ uint64_t sm[WAVES];
-    const uint32_t chunk = (nb + TPB - 1) / TPB;
-    const uint32_t lo_i = min(threadIdx.x * chunk, nb), hi_i = min(lo_i + chunk, nb);
-    uint64_t sum = 0;
-    for (uint32_t i = lo_i; i < hi_i; ++i) sum += tiles[i];
-    uint64_t run = block_excl_scan_u64(sum, sm);
-    for (uint32_t i = lo_i; i < hi_i; ++i) {
-        const uint64_t t = tiles[i];
-        tiles[i] = run;
-        run += t;
-    }
+    scan_top<WAVES>(tiles, nb, sm);
 }
 
 // cum: the items' counts in, their inclusive prefix sum out
 __global__ void __launch_bounds__(TPB) raster_scan_apply_kernel(uint64_t* cum, uint32_t items, const uint64_t* __restrict__ tiles) {
     __shared__ uint64_t sm[WAVES];
-    const uint64_t base = (uint64_t)blockIdx.x * SCAN_TILE + threadIdx.x * 4;
-    uint64_t v[4], sum = 0;
-#pragma unroll
-    for (int k = 0; k < 4; ++k) {
-        v[k] = base + k < items ? cum[base + k] : 0ull;
-        sum += v[k];
-    }
-    uint64_t run = block_excl_scan_u64(sum, sm) + tiles[blockIdx.x];
-#pragma unroll
-    for (int k = 0; k < 4; ++k) {
-        run += v[k];
-        if (base + k < items) cum[base + k] = run;
-    }
+    scan_apply<WAVES, true>(cum, items, tiles, cum, sm);
 }
 
 // Wave w of the grid takes tiles w, w + waves, ...: tile number -> the first item with cum[item] > number -> the tile of that
@@ -417,11 +355,6 @@ MIPSF_SINGLE_FP32 __global__ void __launch_bounds__(TPB) raster_visible_kernel(c
 
 using namespace mipsf;
 
-#define RASTER_ARGS(a, type, name)                                                                                       \
-    MIPSF_REQUIRE((a) != nullptr, name ": null argument block");                                                         \
-    MIPSF_REQUIRE((a)->struct_size == sizeof(type), #type ": struct_size %u, this library expects %u", (a)->struct_size, \
-                  (unsigned)sizeof(type))
-
 static bool intrinsics_ok(double fx, double fy, double cx, double cy) {
     return fx > 0.0 && fx < INFINITY && fy > 0.0 && fy < INFINITY && fabs(cx) < INFINITY && fabs(cy) < INFINITY;
 }
@@ -438,7 +371,7 @@ extern "C" uint64_t mipsf_raster_workspace_bytes(int which, uint32_t n, uint32_t
 }
 
 extern "C" int mipsf_raster_depth(const mipsf_raster_depth_args* a, void* stream) {
-    RASTER_ARGS(a, mipsf_raster_depth_args, "mipsf_raster_depth");
+    MIPSF_ARGS(a, mipsf_raster_depth_args, "mipsf_raster_depth");
     MIPSF_REQUIRE(a->F > 0, "mipsf_raster_depth: a mesh without faces has nothing to render");
     MIPSF_REQUIRE(a->n > 0, "mipsf_raster_depth: no views");
     MIPSF_REQUIRE(a->H > 0 && a->W > 0, "mipsf_raster_depth: an image of %u x %u has no pixels", a->H, a->W);
@@ -480,7 +413,7 @@ extern "C" int mipsf_raster_depth(const mipsf_raster_depth_args* a, void* stream
 }
 
 extern "C" int mipsf_raster_l1(const mipsf_raster_l1_args* a, void* stream) {
-    RASTER_ARGS(a, mipsf_raster_l1_args, "mipsf_raster_l1");
+    MIPSF_ARGS(a, mipsf_raster_l1_args, "mipsf_raster_l1");
     MIPSF_REQUIRE(a->n > 0, "mipsf_raster_l1: no views");
     MIPSF_REQUIRE(a->H > 0 && a->W > 0, "mipsf_raster_l1: an image of %u x %u has no pixels", a->H, a->W);
     MIPSF_REQUIRE(l1_in_range(a->n, a->H, a->W), "mipsf_raster_l1: %u views of %u x %u: at most 65535 views, %u a side, %u pixels a call", a->n,
@@ -496,7 +429,7 @@ extern "C" int mipsf_raster_l1(const mipsf_raster_l1_args* a, void* stream) {
 }
 
 extern "C" int mipsf_raster_visible(const mipsf_raster_visible_args* a, void* stream) {
-    RASTER_ARGS(a, mipsf_raster_visible_args, "mipsf_raster_visible");
+    MIPSF_ARGS(a, mipsf_raster_visible_args, "mipsf_raster_visible");
     if (a->m == 0) return 0;
     MIPSF_REQUIRE(a->points && a->seen, "mipsf_raster_visible: null pointer");
     MIPSF_REQUIRE(a->n == 0 || (a->depth && a->poses && a->max_depth), "mipsf_raster_visible: null pointer");

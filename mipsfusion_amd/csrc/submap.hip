@@ -3,7 +3,7 @@
 //   mipsf_submap_overlap       two launches: centre distances of the related keyframes, then the overlap masks
 // No atomics anywhere: every count is a tree over a workgroup, the surface box goes through at most 256 per-workgroup partials
 // that every workgroup of the second launch folds again for itself.
-#include "common.h"
+#include "block_dev.h"
 #include "../../include/mipsf_submap.h"
 #include "submap_dev.h"
 
@@ -59,51 +59,16 @@ __device__ __forceinline__ void world_point(const Pose& P, const float* __restri
 __device__ __forceinline__ float min32(float a, float b) { return b < a ? b : a; }
 __device__ __forceinline__ float max32(float a, float b) { return b > a ? b : a; }
 
-// workgroup trees; `s` holds one slot per wave; every thread gets the result
-template <int WAVES>
-__device__ __forceinline__ uint32_t block_sum_u(uint32_t v, uint32_t* s) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-    __syncthreads();
-    if ((threadIdx.x & 63) == 0) s[threadIdx.x >> 6] = v;
-    __syncthreads();
-    uint32_t r = 0;
-    for (int w = 0; w < WAVES; ++w) r += s[w];
-    return r;
-}
-__device__ __forceinline__ float block_min_f(float v, float* s) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v = min32(v, __shfl_xor(v, o, 64));
-    __syncthreads();
-    if ((threadIdx.x & 63) == 0) s[threadIdx.x >> 6] = v;
-    __syncthreads();
-    float r = s[0];
-    for (int w = 1; w < SM_WAVES; ++w) r = min32(r, s[w]);
-    return r;
-}
-__device__ __forceinline__ float block_max_f(float v, float* s) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v = max32(v, __shfl_xor(v, o, 64));
-    __syncthreads();
-    if ((threadIdx.x & 63) == 0) s[threadIdx.x >> 6] = v;
-    __syncthreads();
-    float r = s[0];
-    for (int w = 1; w < SM_WAVES; ++w) r = max32(r, s[w]);
-    return r;
-}
-// float64 sum in the order tests/submap_cpu.py spells out: butterfly 32, 16, .. 1 inside a wave, then the waves in ascending order
-__device__ __forceinline__ double block_sum_d(double v, double* s) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v = v + __shfl_xor(v, o, 64);
-    __syncthreads();
-    if ((threadIdx.x & 63) == 0) s[threadIdx.x >> 6] = v;
-    __syncthreads();
-    double r = s[0];
-    for (int w = 1; w < SM_WAVES; ++w) r = r + s[w];
-    return r;
-}
+// the operators of the workgroup trees (block_dev.h); a NaN in b never wins
+struct Min32 {
+    __device__ __forceinline__ float operator()(float a, float b) const { return min32(a, b); }
+};
+struct Max32 {
+    __device__ __forceinline__ float operator()(float a, float b) const { return max32(a, b); }
+};
 
-// sum over a lattice's points: thread t adds points t, t + 256, .. in that order, then block_sum_d.  SM_TPB threads.
+// sum over a lattice's points: thread t adds points t, t + 256, .. in that order, then block_reduce (the float64 order
+// tests/submap_cpu.py spells out: butterfly 32, 16, .. 1 inside a wave, then the waves in ascending order).  SM_TPB threads.
 __device__ __forceinline__ void lattice_sum(const Lattice& l, uint32_t W, const float* __restrict__ rows, const Pose& P, double* s,
                                             double out[3]) {
     double acc[3] = {0.0, 0.0, 0.0};
@@ -113,7 +78,7 @@ __device__ __forceinline__ void lattice_sum(const Lattice& l, uint32_t W, const 
         world_point(P, rows + (size_t)lattice_pixel(l, q, W) * 7, p);
         acc[0] = acc[0] + (double)p[0], acc[1] = acc[1] + (double)p[1], acc[2] = acc[2] + (double)p[2];
     }
-    for (int a = 0; a < 3; ++a) out[a] = block_sum_d(acc[a], s);
+    for (int a = 0; a < 3; ++a) out[a] = block_reduce<SM_WAVES>(acc[a], s, Add());
 }
 
 // ------------------------------------------------------------------------------------------------ frame statistics, launch 1
@@ -139,11 +104,11 @@ MIPSF_SINGLE_FP32 __global__ __launch_bounds__(SM_TPB) void submap_surface_kerne
     }
     uint32_t* out = partial + (size_t)blockIdx.x * 8;
     for (int a = 0; a < 3; ++a) {
-        const float m = block_min_f(lo[a], s_f);
-        const float M = block_max_f(hi[a], s_f);
+        const float m = block_reduce<SM_WAVES>(lo[a], s_f, Min32());
+        const float M = block_reduce<SM_WAVES>(hi[a], s_f, Max32());
         if (threadIdx.x == 0) out[a] = __float_as_uint(m), out[3 + a] = __float_as_uint(M);
     }
-    const uint32_t c = block_sum_u<SM_WAVES>(count, s_u);
+    const uint32_t c = block_reduce<SM_WAVES>(count, s_u, Add());
     if (threadIdx.x == 0) out[6] = c, out[7] = 0u;
 }
 
@@ -174,10 +139,10 @@ MIPSF_SINGLE_FP32 __global__ __launch_bounds__(SM_TPB) void submap_stats_kernel(
     const bool have = tid < c.n_partials;
     const uint32_t* part = c.partial + (size_t)(have ? tid : 0) * 8;
     for (int a = 0; a < 3; ++a) {
-        lo[a] = block_min_f(have ? __uint_as_float(part[a]) : INFINITY, s_f);
-        hi[a] = block_max_f(have ? __uint_as_float(part[3 + a]) : -INFINITY, s_f);
+        lo[a] = block_reduce<SM_WAVES>(have ? __uint_as_float(part[a]) : INFINITY, s_f, Min32());
+        hi[a] = block_reduce<SM_WAVES>(have ? __uint_as_float(part[3 + a]) : -INFINITY, s_f, Max32());
     }
-    const uint32_t n_valid = block_sum_u<SM_WAVES>(have ? part[6] : 0u, s_u);
+    const uint32_t n_valid = block_reduce<SM_WAVES>(have ? part[6] : 0u, s_u, Add());
 
     float bc[3], bl[3];
     for (int a = 0; a < 3; ++a) bc[a] = c.boxes[box * 6 + a], bl[a] = c.boxes[box * 6 + 3 + a];
@@ -215,10 +180,10 @@ MIPSF_SINGLE_FP32 __global__ __launch_bounds__(SM_TPB) void submap_stats_kernel(
         world_point(P, c.rows + (size_t)lattice_pixel(c.B, q, c.W) * 7, p);
         b_raw += submap::inside(p, bc, bl) ? 1u : 0u;
     }
-    a_valid = block_sum_u<SM_WAVES>(a_valid, s_u);
-    a_clamped = block_sum_u<SM_WAVES>(a_clamped, s_u);
-    a_expanded = block_sum_u<SM_WAVES>(a_expanded, s_u);
-    b_raw = block_sum_u<SM_WAVES>(b_raw, s_u);
+    a_valid = block_reduce<SM_WAVES>(a_valid, s_u, Add());
+    a_clamped = block_reduce<SM_WAVES>(a_clamped, s_u, Add());
+    a_expanded = block_reduce<SM_WAVES>(a_expanded, s_u, Add());
+    b_raw = block_reduce<SM_WAVES>(b_raw, s_u, Add());
 
     uint32_t* out = c.record + MIPSF_SUBMAP_HEADER_WORDS + (size_t)box * MIPSF_SUBMAP_BOX_WORDS;
     if (tid == 0) {
@@ -273,7 +238,7 @@ MIPSF_SINGLE_FP32 __global__ __launch_bounds__(SM_TPB) void submap_dist_kernel(D
         acc[0] = acc[0] + (double)(row[0] * d), acc[1] = acc[1] + (double)(row[1] * d), acc[2] = acc[2] + (double)(row[2] * d);
     }
     double m[3];
-    for (int a = 0; a < 3; ++a) m[a] = block_sum_d(acc[a], s_d) / (double)c.rows_per_slot;
+    for (int a = 0; a < 3; ++a) m[a] = block_reduce<SM_WAVES>(acc[a], s_d, Add()) / (double)c.rows_per_slot;
     if (threadIdx.x == 0) {
         const float* M = c.poses + (size_t)blockIdx.x * 16;
         double q = 0.0;
@@ -343,7 +308,7 @@ MIPSF_SINGLE_FP32 __global__ __launch_bounds__(SM_MASK_TPB) void submap_mask_ker
         c.target_d[q] = row[6];
         c.rays_d_cam[q * 3 + 0] = row[0], c.rays_d_cam[q * 3 + 1] = row[1], c.rays_d_cam[q * 3 + 2] = row[2];
     }
-    count = block_sum_u<SM_MASK_TPB / MIPSF_WAVE>(count, s_u);
+    count = block_reduce<SM_MASK_TPB / MIPSF_WAVE>(count, s_u, Add());
     if (tid == 0) c.count[0] = count;
 }
 
@@ -359,9 +324,7 @@ using namespace mipsf;
 
 extern "C" int mipsf_submap_frame_stats(const mipsf_submap_frame_stats_args* a, void* stream) {
     static const char* who = "mipsf_submap_frame_stats";
-    MIPSF_REQUIRE(a != nullptr, "%s: null argument block", who);
-    MIPSF_REQUIRE(a->struct_size == sizeof(mipsf_submap_frame_stats_args), "mipsf_submap_frame_stats_args: struct_size %u, this library expects %u",
-                  a->struct_size, (unsigned)sizeof(mipsf_submap_frame_stats_args));
+    MIPSF_ARGS(a, mipsf_submap_frame_stats_args, who);
     MIPSF_REQUIRE(a->H >= 1 && a->W >= 1 && (uint64_t)a->H * a->W <= (1ull << 28), "%s: image %u x %u", who, a->H, a->W);
     MIPSF_REQUIRE(a->n_boxes >= 1 && a->n_boxes <= MIPSF_SUBMAP_MAX_BOXES, "%s: %u sub-maps, accepted are 1 .. %u", who, a->n_boxes,
                   MIPSF_SUBMAP_MAX_BOXES);
@@ -388,9 +351,7 @@ extern "C" int mipsf_submap_frame_stats(const mipsf_submap_frame_stats_args* a, 
 
 extern "C" int mipsf_submap_overlap(const mipsf_submap_overlap_args* a, void* stream) {
     static const char* who = "mipsf_submap_overlap";
-    MIPSF_REQUIRE(a != nullptr, "%s: null argument block", who);
-    MIPSF_REQUIRE(a->struct_size == sizeof(mipsf_submap_overlap_args), "mipsf_submap_overlap_args: struct_size %u, this library expects %u",
-                  a->struct_size, (unsigned)sizeof(mipsf_submap_overlap_args));
+    MIPSF_ARGS(a, mipsf_submap_overlap_args, who);
     MIPSF_REQUIRE(a->H >= 1 && a->W >= 1 && (uint64_t)a->H * a->W <= (1ull << 28), "%s: image %u x %u", who, a->H, a->W);
     if (check_lattice(who, "C", a->H, a->W, a->lat_h, a->lat_w)) return 1;
     MIPSF_REQUIRE(a->k <= MIPSF_SUBMAP_MAX_TOP_KF, "%s: %u chosen keyframes, accepted are at most %u", who, a->k, MIPSF_SUBMAP_MAX_TOP_KF);

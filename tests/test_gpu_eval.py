@@ -55,6 +55,34 @@ def test_samples_equal_the_restatement(dev, name):
             assert np.array_equal(_words(got_p.cpu().numpy()), _words(want_p)), (name, n, seed)
 
 
+def _box_faces(m, first=None):
+    v, f = E.tessellated_box((0, 0, 0), (3, 2, 1), m=m)
+    return np.asarray(v, np.float32), f[:first]
+
+
+# the prefix sum of the faces' areas (csrc/block_dev.h's device-wide scan, uint64, inclusive) around one tile of 1024 faces and
+# on either side of 256 tiles: past them a thread of the one-block top scan owns two tile sums.  At m = 148 the restatement's
+# 4096 samples land on 4096 distinct faces from index 66 to 262 838, so a wrong tile offset anywhere shows.
+SCAN_EDGE_MESHES = {
+    "1023_faces": lambda: _box_faces(10, 1023),
+    "1024_faces": lambda: _box_faces(10, 1024),
+    "1025_faces": lambda: _box_faces(10, 1025),
+    "254_tiles": lambda: _box_faces(147),
+    "257_tiles": lambda: _box_faces(148),
+}
+
+
+@pytest.mark.parametrize("name", sorted(SCAN_EDGE_MESHES))
+def test_samples_equal_the_restatement_around_the_scan_tiles(dev, name):
+    v32, f = SCAN_EDGE_MESHES[name]()
+    assert f.shape[0] == {"1023_faces": 1023, "1024_faces": 1024, "1025_faces": 1025, "254_tiles": 259308, "257_tiles": 262848}[name]
+    want_p, want_f, want_area = E.sample_surface(v32, f, 4096, 7)
+    got_p, got_f, got_area = ev.sample_surface(v32, f, 4096, 7)
+    assert got_area == want_area
+    assert np.array_equal(got_f.cpu().numpy(), want_f)
+    assert np.array_equal(_words(got_p.cpu().numpy()), _words(want_p))
+
+
 def test_sampler_accepts_a_mesh_and_tensors(dev):
     v, f = _box_room()
     want = E.sample_surface(v.astype(np.float32), f, 1000, 3)

@@ -78,6 +78,24 @@ def test_cloud_keeps_rows_with_depth_in_order(dev):
         assert mm == w.shape[0] and _ulp_close(gg.cpu().numpy(), w.numpy(), 2)
 
 
+@pytest.mark.parametrize("n", [1023, 1024, 1025, 262145])
+def test_cloud_compaction_equals_numpy_around_the_scan_tiles(dev, n):
+    """flag, scan, emit with the device-wide scan of csrc/block_dev.h (uint32, exclusive): one tile of 1024 rows, either side of
+    it, and just past 256 tiles, where a thread of the one-block top scan owns two tile sums.  About half the rows have no depth.
+    Under the identity pose a kept row's point is fl(direction * depth), one fp32 rounding, so the cloud is compared with numpy's
+    boolean compaction for equality."""
+    g = np.random.default_rng(n)
+    rows = np.zeros((n, 7), np.float32)
+    rows[:, :3] = g.standard_normal((n, 3), dtype=np.float32)
+    rows[:, 6] = np.where(g.random(n) < 0.5, g.uniform(0.5, 4.0, n), 0.0).astype(np.float32)
+    keep = rows[:, 6] > 0
+    assert 0.4 * n < keep.sum() < 0.6 * n
+    want = (rows[:, :3] * rows[:, 6:7])[keep]
+    got, m = pc.cloud_from_rays(torch.from_numpy(rows).to(dev), n, torch.eye(4).reshape(1, 4, 4).to(dev).contiguous())
+    assert m == want.shape[0]
+    assert np.array_equal(got.cpu().numpy(), want)
+
+
 # ------------------------------------------------------------------------------------------- 2. bin + nearest neighbour
 def _check_nearest(dev, src, tgt, max_dist, max_cells=None):
     j, d2 = R.nearest_cpu(np.asarray(src, np.float64), tgt, max_dist)
