@@ -16,6 +16,7 @@ _SUBMAP_MANAGER = ("SubmapManager", "Decision", "derive_schedule", "frame_stats_
 _EVALUATE = ("sample_surface", "nearest_distance", "distance_stats", "reconstruction_metrics", "cull_to_views", "ReconMetrics",
              "DistanceStats")
 _MESH_RENDER = ("render_mesh_depth", "depth_l1", "visible_points", "DepthMetrics")
+_TSDF = ("TSDFVolume", "TSDFCounts", "tsdf_mesh_from_frames", "mesh_from_rendered_depth")
 
 
 def __getattr__(name):
@@ -41,4 +42,7 @@ def __getattr__(name):
     if name in _MESH_RENDER:                # a mesh as depth images, depth L1, occlusion (mipsfusion_amd/mesh_render.py), the same way
         from . import mesh_render
         return getattr(mesh_render, name)
+    if name in _TSDF:                       # depth frames fused into a TSDF volume and meshed (mipsfusion_amd/tsdf.py), the same way
+        from . import tsdf
+        return getattr(tsdf, name)
     raise AttributeError(f"module {__name__!r} has no attribute {name!r}")

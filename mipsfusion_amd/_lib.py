@@ -354,6 +354,24 @@ RASTER_SIGNATURES = {
 }
 
 
+# include/mipsf_tsdf.h (depth frames fused into a TSDF volume; the colour of marched vertices)
+TSDF_MAX_VOXELS, TSDF_MAX_SIDE, TSDF_VIEW_CHUNK, TSDF_BRICK = 0x7FFFFFFF, 8192, 256, (8, 8, 16)
+TSDF_NO_CULL = 1
+TSDF_MAX_BRICKS = 0xFFFFFF
+TSDF_RECORD_WORDS = 2                      # uint64 updates, observed
+TsdfIntegrateArgs = _args("TsdfIntegrateArgs", [("X", _CU), ("Y", _CU), ("Z", _CU), ("n", _CU), ("H", _CU), ("W", _CU), ("flags", _CU),
+                                                ("fx", C.c_double), ("fy", C.c_double), ("cx", C.c_double), ("cy", C.c_double),
+                                                ("trunc", C.c_double), ("depth_max", C.c_double), ("max_weight", C.c_double),
+                                                ("ticks", _VP * 3), ("depth", _VP), ("rgb", _VP), ("poses", _VP), ("tsdf", _VP),
+                                                ("weight", _VP), ("color", _VP), ("record", _VP)])
+TsdfSampleArgs = _args("TsdfSampleArgs", [("X", _CU), ("Y", _CU), ("Z", _CU), ("m", _CU), ("reserved", _CU), ("points", _VP),
+                                          ("weight", _VP), ("color", _VP), ("out", _VP)])
+TSDF_SIGNATURES = {
+    "mipsf_tsdf_integrate": (_I, [C.POINTER(TsdfIntegrateArgs), _P]),
+    "mipsf_tsdf_sample": (_I, [C.POINTER(TsdfSampleArgs), _P]),
+}
+
+
 def buffer_size(which: int, n: int = 0, a: int = 0, b: int = 0, meta=None) -> int:
     """mipsf_buffer_size: elements of a scratch / record buffer (SIZE_* above)."""
     v = lib().mipsf_buffer_size(which, n, a, b, C.byref(meta) if meta is not None else None)
@@ -378,7 +396,7 @@ def lib() -> C.CDLL:
                                        + list(FUSE_SIGNATURES.items()) + list(ICP_SIGNATURES.items())
                                        + list(COMPACT_SIGNATURES.items()) + list(POSEGRAPH_SIGNATURES.items())
                                        + list(SUBMAP_SIGNATURES.items()) + list(EVAL_SIGNATURES.items())
-                                       + list(RASTER_SIGNATURES.items())):
+                                       + list(RASTER_SIGNATURES.items()) + list(TSDF_SIGNATURES.items())):
             fn = getattr(handle, name)
             fn.restype = res
             fn.argtypes = args

@@ -1,0 +1,242 @@
+"""Depth frames fused into a dense TSDF volume on the GPU, and the volume as a mesh.  The step between depth images and a volume:
+the rendered-depth meshing protocol of the papers that followed the reference (render depth from the neural map at the estimated
+poses, TSDF-fuse the images, march), the classical baseline (fuse the sensor depth), and a stand-in ground truth for a sequence
+that has none.  Upstream fuses with a host library; here it is the kernel of ``csrc/tsdf.hip`` (C ABI: include/mipsf_tsdf.h;
+DESIGN.md 4.19):
+
+    TSDFVolume                 the state (tsdf, weight, optionally colour, all on the device) and integrate / volume / extract_mesh
+    tsdf_mesh_from_frames      depth frames + poses -> mesh.Mesh
+    mesh_from_rendered_depth   model + poses -> rendered depth -> mesh.Mesh
+
+The tsdf, weight and colour words EQUAL those of the float64 restatement in tests/tsdf_cpu.py: the rule is fixed operation by
+operation in the header and a voxel takes its views in ascending order, whatever the cut into calls.  There is no CPU fallback.
+"""
+from __future__ import annotations
+
+import ctypes as C
+import math
+from typing import NamedTuple, Optional
+
+import numpy as np
+import torch
+
+from . import _lib
+from .mesh import Mesh, marching_cubes, save_ply
+from .mesh_render import _poses
+from .scene_mesh import _intrinsics
+
+
+class TSDFCounts(NamedTuple):
+    updates: int                     # (voxel, view) pairs that updated, over the calls of one integrate()
+    observed: int                    # voxels whose weight is positive afterwards
+
+
+def _device(device=None) -> torch.device:
+    if not torch.cuda.is_available():
+        raise RuntimeError("mipsfusion_amd.tsdf runs on the GPU only (no CPU fallback exists)")
+    if device is None:
+        return torch.device("cuda", torch.cuda.current_device())
+    device = torch.device(device)
+    if device.type != "cuda":
+        raise RuntimeError("mipsfusion_amd.tsdf runs on the GPU only (no CPU fallback exists)")
+    return torch.device("cuda", torch.cuda.current_device() if device.index is None else device.index)
+
+
+def _images(a, dev, channels: int, what: str) -> torch.Tensor:
+    """host or device, one image or a stack, a list of images -> fp32 [n,H,W] (channels = 0) or [n,H,W,3] on dev; a device fp32
+    contiguous tensor is taken as it is"""
+    if not torch.is_tensor(a):
+        a = torch.stack([torch.as_tensor(np.asarray(x) if not torch.is_tensor(x) else x) for x in a]) if isinstance(a, (list, tuple)) \
+            else torch.as_tensor(np.asarray(a))
+    want = 3 if channels == 0 else 4
+    if a.dim() == want - 1:
+        a = a[None]
+    if a.dim() != want or (channels and a.shape[-1] != channels):
+        raise ValueError(f"{what}: expected [n,H,W{',3' if channels else ''}] or one image, got {tuple(a.shape)}")
+    return a.to(dev).to(torch.float32).contiguous()
+
+
+class TSDFVolume:
+    """A dense TSDF volume on the device.  Voxel (i,j,k) sits at origin + voxel_size * (i,j,k) (float64, rounded to fp32 by the
+    kernel); ``trunc`` is the truncation distance in metres.  tsdf is in units of trunc: 1 in free space, 0 on the surface,
+    negative behind it down to -1; weight counts the views that updated the voxel, capped at ``max_weight``."""
+
+    def __init__(self, origin, voxel_size: float, dims, trunc: float, color: bool = False, max_weight: float = math.inf, device=None):
+        self.origin = np.asarray(origin, np.float64).reshape(3).copy()
+        self.voxel_size, self.trunc, self.max_weight = float(voxel_size), float(trunc), float(max_weight)
+        self.dims = tuple(int(d) for d in dims)
+        if len(self.dims) != 3 or min(self.dims) < 1:
+            raise ValueError(f"dims: expected three positive counts, got {dims}")
+        if not (self.voxel_size > 0 and math.isfinite(self.voxel_size)):
+            raise ValueError(f"voxel_size {voxel_size} is not positive and finite")
+        n = self.dims[0] * self.dims[1] * self.dims[2]
+        if n > _lib.TSDF_MAX_VOXELS:
+            raise ValueError(f"a grid of {self.dims[0]} x {self.dims[1]} x {self.dims[2]} voxels at voxel size {self.voxel_size} has "
+                             f"2^31 voxels or more; choose a larger voxel size or smaller bounds")
+        self.device = _device(device)
+        self.ticks = tuple(self.origin[a] + self.voxel_size * np.arange(self.dims[a], dtype=np.float64) for a in range(3))
+        with torch.cuda.device(self.device):
+            self._ticks_dev = tuple(torch.from_numpy(t).to(self.device) for t in self.ticks)
+            self.tsdf = torch.zeros(self.dims, dtype=torch.float32, device=self.device)
+            self.weight = torch.zeros(self.dims, dtype=torch.float32, device=self.device)
+            self.color = torch.zeros(self.dims + (3,), dtype=torch.float32, device=self.device) if color else None
+
+    def reset(self) -> None:
+        for t in (self.tsdf, self.weight, self.color):
+            if t is not None:
+                t.zero_()
+
+    # ----------------------------------------------------------------------------------------------------------- enqueue only
+    def integrate_enqueue(self, depth: torch.Tensor, poses: torch.Tensor, K, rgb: Optional[torch.Tensor] = None,
+                          depth_max: float = math.inf, record: Optional[torch.Tensor] = None, flags: int = 0) -> torch.Tensor:
+        """One launch of mipsf_tsdf_integrate; nothing is read back.  depth fp32 [n,H,W], poses fp32 [n,4,4], rgb fp32 [n,H,W,3]
+        or None, all on the device -> record int64 [2] on the device: (voxel, view) pairs updated, voxels with a positive weight"""
+        _lib.dptr(depth), _lib.dptr(poses), _lib.dptr(rgb)
+        if depth.dim() != 3 or tuple(poses.shape) != (depth.shape[0], 4, 4):
+            raise ValueError(f"expected depth [n,H,W] and poses [n,4,4], got {tuple(depth.shape)} and {tuple(poses.shape)}")
+        if rgb is not None and tuple(rgb.shape) != tuple(depth.shape) + (3,):
+            raise ValueError(f"rgb: expected {tuple(depth.shape) + (3,)}, got {tuple(rgb.shape)}")
+        if (rgb is None) != (self.color is None):
+            raise ValueError("rgb goes with a volume made with color=True, and such a volume needs rgb")
+        fx, fy, cx, cy = (float(x) for x in _intrinsics(K))
+        n, H, W = depth.shape
+        with torch.cuda.device(self.device):
+            record = torch.empty(_lib.TSDF_RECORD_WORDS, dtype=torch.int64, device=self.device) if record is None else record
+            a = _lib.TsdfIntegrateArgs.new(X=self.dims[0], Y=self.dims[1], Z=self.dims[2], n=n, H=H, W=W, flags=int(flags), fx=fx, fy=fy,
+                                           cx=cx, cy=cy, trunc=self.trunc, depth_max=float(depth_max), max_weight=self.max_weight,
+                                           depth=depth.data_ptr(), rgb=None if rgb is None else rgb.data_ptr(), poses=poses.data_ptr(),
+                                           tsdf=_lib.dptr(self.tsdf), weight=_lib.dptr(self.weight), color=_lib.dptr(self.color),
+                                           record=_lib.dptr(record, torch.int64))
+            for d in range(3):
+                a.ticks[d] = _lib.dptr(self._ticks_dev[d], torch.float64)
+            _lib.check(_lib.lib().mipsf_tsdf_integrate(C.byref(a), _lib.stream_ptr()), "tsdf_integrate")
+        return record
+
+    def sample_enqueue(self, points: torch.Tensor) -> torch.Tensor:
+        """points float64 [m,3] in index units on the device -> colour fp32 [m,3] on the device (mipsf_tsdf_sample)"""
+        if self.color is None:
+            raise ValueError("the volume was made without colour")
+        if points.dim() != 2 or points.shape[1] != 3:
+            raise ValueError(f"points: expected [m,3], got {tuple(points.shape)}")
+        m = points.shape[0]
+        with torch.cuda.device(self.device):
+            out = torch.empty(max(m, 1), 3, dtype=torch.float32, device=self.device)[:m]
+            a = _lib.TsdfSampleArgs.new(X=self.dims[0], Y=self.dims[1], Z=self.dims[2], m=m, points=_lib.dptr(points, torch.float64),
+                                        weight=_lib.dptr(self.weight), color=_lib.dptr(self.color), out=out.data_ptr())
+            _lib.check(_lib.lib().mipsf_tsdf_sample(C.byref(a), _lib.stream_ptr()), "tsdf_sample")
+        return out
+
+    # ----------------------------------------------------------------------------------------------------------- public
+    def integrate(self, depth, c2w, K, rgb=None, depth_max: float = math.inf, views_per_call: Optional[int] = None) -> TSDFCounts:
+        """Fuses the views in the order given.  depth [n,H,W] or [H,W] (0 = no measurement), c2w [n,4,4] or [4,4] (camera to world,
+        the datasets' OpenGL convention), K a 3x3 matrix or (fx, fy, cx, cy), rgb [n,H,W,3] in a colour volume; host or device
+        arrays, lists of them too.  The views are cut into calls of ``views_per_call`` (all in one by default); the cut does not
+        reach the bytes.  One read-back of 16 bytes per call."""
+        with torch.cuda.device(self.device):
+            D = _images(depth, self.device, 0, "depth")
+            P = _poses(c2w, self.device)
+            C3 = None if rgb is None else _images(rgb, self.device, 3, "rgb")
+            n = D.shape[0]
+            if P.shape[0] != n:
+                raise ValueError(f"{n} depth images and {P.shape[0]} poses")
+            per = max(n, 1) if views_per_call is None else int(views_per_call)
+            if per < 1:
+                raise ValueError("views_per_call must be positive")
+            records = [self.integrate_enqueue(D[k:k + per], P[k:k + per], K, None if C3 is None else C3[k:k + per], depth_max)
+                       for k in range(0, max(n, 1), per)]
+            got = torch.stack(records).cpu().numpy()
+        return TSDFCounts(int(got[:, 0].sum()), int(got[-1, 1]))
+
+    def volume(self, min_weight: float = 1.0) -> torch.Tensor:
+        """the marching input: tsdf where weight >= min_weight, -inf (unobserved, off for the marcher) elsewhere"""
+        return torch.where(self.weight >= float(min_weight), self.tsdf, torch.full_like(self.tsdf, -math.inf))
+
+    def extract_mesh(self, min_weight: float = 1.0, mesh_savepath: str = "") -> Mesh:
+        """marching_cubes(volume(min_weight), 0, truncation=1): saturated voxels (tsdf = 1) switch their cells off like unobserved
+        ones.  -> Mesh with world vertices in float64 and per-vertex colours when colour was fused."""
+        if min(self.dims) < 2:
+            v, f = torch.zeros(0, 3, dtype=torch.float64, device=self.device), torch.zeros(0, 3, dtype=torch.int64, device=self.device)
+        else:
+            with torch.cuda.device(self.device):
+                v, f = marching_cubes(self.volume(min_weight), 0.0, truncation=1.0, return_device=True)
+        colors = None
+        if self.color is not None:
+            colors = self.sample_enqueue(v.contiguous()).cpu().numpy()
+        vertices = self.origin + v.cpu().numpy() * self.voxel_size
+        mesh = Mesh(vertices, f.cpu().numpy(), colors)
+        if mesh_savepath:
+            save_ply(mesh_savepath, mesh.vertices, mesh.faces, mesh.vertex_colors)
+        return mesh
+
+
+def frames_bounds(depth: torch.Tensor, poses: torch.Tensor, K, depth_max: float = math.inf) -> np.ndarray:
+    """the box of the back-projected usable pixels (0 < d < inf, d <= depth_max) of device depth [n,H,W] -> float64 [3,2];
+    float64 on the device, six numbers read back"""
+    fx, fy, cx, cy = (float(x) for x in _intrinsics(K))
+    n, H, W = depth.shape
+    dev = depth.device
+    jj, ii = torch.meshgrid(torch.arange(H, dtype=torch.float64, device=dev), torch.arange(W, dtype=torch.float64, device=dev), indexing="ij")
+    dirs = torch.stack([(ii - cx) / fx, -((jj - cy) / fy), -torch.ones_like(ii)], -1)                    # [H,W,3]
+    lo = torch.full((3,), math.inf, dtype=torch.float64, device=dev)
+    hi = -lo
+    for k in range(0, n, 8):                                                                             # 8 views at a time: 55 MB at 460 x 620
+        d = depth[k:k + 8].to(torch.float64)
+        ok = ((d > 0) & (d < math.inf) & (d <= depth_max))[..., None]
+        P = poses[k:k + 8].to(torch.float64)
+        p = torch.einsum("vhwc,vdc->vhwd", dirs * d[..., None], P[:, :3, :3]) + P[:, None, None, :3, 3]
+        big = torch.full_like(p, math.inf)
+        lo = torch.minimum(lo, torch.where(ok, p, big).reshape(-1, 3).amin(0))
+        hi = torch.maximum(hi, torch.where(ok, p, -big).reshape(-1, 3).amax(0))
+    out = torch.stack([lo, hi], 1).cpu().numpy()
+    if not np.all(np.isfinite(out)):
+        raise ValueError("no pixel with a usable depth: give bounds")
+    return out
+
+
+def tsdf_mesh_from_frames(depth, c2w, K, voxel_size: float, trunc: Optional[float] = None, rgb=None, bounds=None,
+                          depth_max: float = math.inf, min_weight: float = 1.0, mesh_savepath: str = "", device=None,
+                          return_volume: bool = False):
+    """Depth frames -> Mesh: a volume over ``bounds`` ([3,2], by default the box of the back-projected usable pixels padded by
+    trunc) with ``voxel_size``, all views fused, marched.  ``trunc`` defaults to 4 voxels.  Device tensors are used where they
+    lie; ``return_volume`` adds the TSDFVolume."""
+    voxel_size = float(voxel_size)
+    trunc = 4.0 * voxel_size if trunc is None else float(trunc)
+    dev = depth.device if torch.is_tensor(depth) and depth.is_cuda else _device(device)
+    with torch.cuda.device(dev):
+        D = _images(depth, dev, 0, "depth")
+        P = _poses(c2w, dev)
+        C3 = None if rgb is None else _images(rgb, dev, 3, "rgb")
+        if bounds is None:
+            b = frames_bounds(D, P, K, depth_max)
+            b[:, 0] -= trunc
+            b[:, 1] += trunc
+        else:
+            b = np.asarray(bounds.detach().cpu() if torch.is_tensor(bounds) else bounds, np.float64).reshape(3, 2)
+        counts = np.ceil((b[:, 1] - b[:, 0]) / voxel_size)
+        if not (np.all(np.isfinite(counts)) and np.all(counts >= 0)):
+            raise ValueError(f"bounds {b.tolist()} at voxel size {voxel_size}")
+        dims = [int(c) + 1 for c in counts]
+        if dims[0] * dims[1] * dims[2] > _lib.TSDF_MAX_VOXELS:
+            raise ValueError(f"voxel size {voxel_size} over bounds {b.tolist()} gives a grid of {dims[0]} x {dims[1]} x {dims[2]}: 2^31 voxels "
+                             f"or more; choose a larger voxel size")
+        vol = TSDFVolume(b[:, 0], voxel_size, dims, trunc, color=C3 is not None, device=dev)
+        vol.integrate(D, P, K, C3, depth_max)
+        mesh = vol.extract_mesh(min_weight, mesh_savepath)
+    return (mesh, vol) if return_volume else mesh
+
+
+@torch.no_grad()
+def mesh_from_rendered_depth(model, rays_d_cam, poses_local, first_kf_c2w, H: int, W: int, K, voxel_size: float,
+                             trunc: Optional[float] = None, color: bool = True, bounds=None, depth_max: float = math.inf,
+                             min_weight: float = 1.0, mesh_savepath: str = "", ray_batch_size: int = 10000, return_volume: bool = False):
+    """The rendered-depth meshing protocol: inference.render_full_img per local pose with no depth guidance, the images fused at
+    first_kf_c2w @ pose_local, the volume marched.  No arithmetic of its own."""
+    from .inference import render_full_img
+    dev = model.embed_fn.params.device
+    local = _poses(poses_local, dev)
+    first = torch.as_tensor(np.asarray(first_kf_c2w) if not torch.is_tensor(first_kf_c2w) else first_kf_c2w).to(dev).to(torch.float32)
+    images = [render_full_img(model, rays_d_cam, p, None, int(H), int(W), ray_batch_size) for p in local]
+    depth = torch.stack([d for _, d in images]).to(torch.float32)
+    rgb = torch.stack([c for c, _ in images]).to(torch.float32) if color else None
+    return tsdf_mesh_from_frames(depth, first @ local, K, voxel_size, trunc, rgb, bounds, depth_max, min_weight, mesh_savepath,
+                                 device=dev, return_volume=return_volume)
