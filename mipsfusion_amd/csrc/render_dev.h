@@ -80,7 +80,11 @@ __device__ __forceinline__ void store_ray_outputs(uint32_t n, float a_r, float a
     rgb_out[3 * n] = a_r, rgb_out[3 * n + 1] = a_g, rgb_out[3 * n + 2] = a_b;
     depth_out[n] = a_d;
     if (var_out) var_out[n] = a_v;
-    if (disp_out) disp_out[n] = 1.0f / fmaxf(1e-10f, a_d / a_w);
+    if (disp_out) {
+        // a ray whose weights all underflowed has 0 / 0 here: torch.max keeps the NaN (scene_rep.py:100), fmaxf would drop it
+        const float q = a_d / a_w;
+        disp_out[n] = 1.0f / (q != q ? q : fmaxf(1e-10f, q));
+    }
     if (acc_out) acc_out[n] = a_w;
 }
 

@@ -760,6 +760,7 @@ def test_render_losses_finished_in_the_render_launch(dev):
     16-ray workgroup partly empty and that need one / several workgroups, at sample counts on both sides of the one-launch
     forms' threshold (S <= 128: render_train_kernel, above: render_fwd_kernel); the ticket is left at zero and repeated calls
     agree bit for bit."""
+    # (kernel against kernel, random `counts`; the independent float64 answer: tests/test_gpu_render_fp64.py)
     import ctypes as C
     from mipsfusion_amd._lib import dptr, lib, stream_ptr
     torch.manual_seed(12)
@@ -808,6 +809,7 @@ def test_render_backward_written_by_the_forward_launch(dev):
     g_total = 1 bit for bit (EMD on and off, rays without depth, partly empty workgroups, one and two samples per lane);
     KEEP_IF_UNIT leaves the buffer alone for g_total = 1 and rewrites it -- bit-equal to the plain backward -- otherwise; through
     autograd every way of calling backward gives the gradients of the unfused path."""
+    # (kernel against kernel, random `counts`; the independent float64 answer: tests/test_gpu_render_fp64.py)
     import ctypes as C
     from mipsfusion_amd._lib import dptr, lib, stream_ptr
     from mipsfusion_amd.helper_functions.utils import backward_from_one
