@@ -17,6 +17,9 @@ _EVALUATE = ("sample_surface", "nearest_distance", "distance_stats", "reconstruc
              "DistanceStats")
 _MESH_RENDER = ("render_mesh_depth", "depth_l1", "visible_points", "DepthMetrics")
 _TSDF = ("TSDFVolume", "TSDFCounts", "tsdf_mesh_from_frames", "mesh_from_rendered_depth")
+# (the function image_metrics.image_metrics is reached through its module: the package attribute of that name IS the module)
+_IMAGE_METRICS = ("psnr", "ssim", "ms_ssim", "render_metrics", "gaussian_window", "ImageMetrics", "RenderMetrics")
+_TRAJECTORY = ("align_trajectory", "trajectory_metrics", "TrajectoryMetrics")
 
 
 def __getattr__(name):
@@ -45,4 +48,10 @@ def __getattr__(name):
     if name in _TSDF:                       # depth frames fused into a TSDF volume and meshed (mipsfusion_amd/tsdf.py), the same way
         from . import tsdf
         return getattr(tsdf, name)
+    if name in _IMAGE_METRICS:              # rendered frames against captured ones: PSNR, SSIM, MS-SSIM (mipsfusion_amd/image_metrics.py)
+        from . import image_metrics
+        return getattr(image_metrics, name)
+    if name in _TRAJECTORY:                 # aligned absolute trajectory error, host only (mipsfusion_amd/trajectory.py)
+        from . import trajectory
+        return getattr(trajectory, name)
     raise AttributeError(f"module {__name__!r} has no attribute {name!r}")

@@ -372,6 +372,36 @@ TSDF_SIGNATURES = {
 }
 
 
+# include/mipsf_image.h (two image stacks compared: error sums, valid-region SSIM and its cs term, the MS-SSIM pyramid's 2 x 2 mean)
+IMAGE_F32, IMAGE_F64 = 0, 1
+IMAGE_WINDOW, IMAGE_TILE_H, IMAGE_TILE_W, IMAGE_MAX_CHANNELS, IMAGE_MAX_SIDE = 11, 16, 32, 4, 8192
+IMAGE_MAX_PLANES, IMAGE_MAX_VALUES, IMAGE_ERROR_MAX_BLOCKS = 65535, 0x7FFFFFFF, 256
+IMAGE_WS_ERROR, IMAGE_WS_SSIM = 1, 2
+IMAGE_ERROR_RECORD_BYTES, IMAGE_SSIM_RECORD_BYTES = 32, 32
+
+
+class ImageErrorRecord(C.Structure):
+    _fields_ = [("sum_sq", C.c_double), ("sum_abs", C.c_double), ("max_abs", C.c_double), ("count", C.c_uint64)]
+
+
+class ImageSsimRecord(C.Structure):
+    _fields_ = [("sum_ssim", C.c_double), ("sum_cs", C.c_double), ("count", C.c_uint64), ("reserved", C.c_uint64)]
+
+
+ImageErrorArgs = _args("ImageErrorArgs", [("n", _CU), ("H", _CU), ("W", _CU), ("C", _CU), ("dtype", _CU), ("a", _VP), ("b", _VP),
+                                          ("records", _VP), ("workspace", _VP)])
+ImageSsimArgs = _args("ImageSsimArgs", [("n", _CU), ("H", _CU), ("W", _CU), ("C", _CU), ("dtype", _CU), ("window", C.c_double * 11),
+                                        ("C1", C.c_double), ("C2", C.c_double), ("a", _VP), ("b", _VP), ("records", _VP),
+                                        ("workspace", _VP)])
+ImagePool2Args = _args("ImagePool2Args", [("n", _CU), ("H", _CU), ("W", _CU), ("C", _CU), ("dtype", _CU), ("in_", _VP), ("out", _VP)])
+IMAGE_SIGNATURES = {
+    "mipsf_image_workspace_bytes": (_U64, [_I, _U32, _U32, _U32, _U32]),
+    "mipsf_image_error": (_I, [C.POINTER(ImageErrorArgs), _P]),
+    "mipsf_image_ssim": (_I, [C.POINTER(ImageSsimArgs), _P]),
+    "mipsf_image_pool2": (_I, [C.POINTER(ImagePool2Args), _P]),
+}
+
+
 def buffer_size(which: int, n: int = 0, a: int = 0, b: int = 0, meta=None) -> int:
     """mipsf_buffer_size: elements of a scratch / record buffer (SIZE_* above)."""
     v = lib().mipsf_buffer_size(which, n, a, b, C.byref(meta) if meta is not None else None)
@@ -396,7 +426,8 @@ def lib() -> C.CDLL:
                                        + list(FUSE_SIGNATURES.items()) + list(ICP_SIGNATURES.items())
                                        + list(COMPACT_SIGNATURES.items()) + list(POSEGRAPH_SIGNATURES.items())
                                        + list(SUBMAP_SIGNATURES.items()) + list(EVAL_SIGNATURES.items())
-                                       + list(RASTER_SIGNATURES.items()) + list(TSDF_SIGNATURES.items())):
+                                       + list(RASTER_SIGNATURES.items()) + list(TSDF_SIGNATURES.items())
+                                       + list(IMAGE_SIGNATURES.items())):
             fn = getattr(handle, name)
             fn.restype = res
             fn.argtypes = args
