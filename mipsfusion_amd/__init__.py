@@ -16,7 +16,7 @@ _SUBMAP_MANAGER = ("SubmapManager", "Decision", "derive_schedule", "frame_stats_
 _EVALUATE = ("sample_surface", "nearest_distance", "distance_stats", "reconstruction_metrics", "cull_to_views", "ReconMetrics",
              "DistanceStats")
 _MESH_RENDER = ("render_mesh_depth", "depth_l1", "visible_points", "DepthMetrics")
-_TSDF = ("TSDFVolume", "TSDFCounts", "tsdf_mesh_from_frames", "mesh_from_rendered_depth")
+_TSDF = ("TSDFVolume", "TSDFCounts", "tsdf_mesh_from_frames", "mesh_from_rendered_depth", "Raycast", "TrackResult", "tsdf_odometry")
 # (the function image_metrics.image_metrics is reached through its module: the package attribute of that name IS the module)
 _IMAGE_METRICS = ("psnr", "ssim", "ms_ssim", "render_metrics", "gaussian_window", "ImageMetrics", "RenderMetrics")
 _TRAJECTORY = ("align_trajectory", "trajectory_metrics", "TrajectoryMetrics")

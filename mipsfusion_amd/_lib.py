@@ -372,6 +372,30 @@ TSDF_SIGNATURES = {
 }
 
 
+# include/mipsf_track.h (the volume as depth, normal and colour images by ray casting; a depth frame registered against them)
+TRACK_MAX_SAMPLES, TRACK_TILE, TRACK_RESULT_DOUBLES, TRACK_MAX_ITERATION, TRACK_MAX_VIEWS = 0x100000, 16, 20, 1000, 65535
+TRACK_NO_SKIP = 1
+TRACK_WS_RAYCAST, TRACK_WS_REGISTER = 1, 2
+TRACK_RECORD_WORDS = 2                     # uint64 hits, marked
+TrackRaycastArgs = _args("TrackRaycastArgs", [("X", _CU), ("Y", _CU), ("Z", _CU), ("n", _CU), ("H", _CU), ("W", _CU), ("flags", _CU),
+                                              ("origin", C.c_double * 3), ("voxel", C.c_double), ("trunc", C.c_double),
+                                              ("fx", C.c_double), ("fy", C.c_double), ("cx", C.c_double), ("cy", C.c_double),
+                                              ("near", C.c_double), ("far", C.c_double), ("step", C.c_double), ("min_weight", C.c_double),
+                                              ("tsdf", _VP), ("weight", _VP), ("color", _VP), ("poses", _VP), ("depth", _VP),
+                                              ("normals", _VP), ("color_out", _VP), ("record", _VP), ("workspace", _VP)])
+TrackRegisterArgs = _args("TrackRegisterArgs", [("H", _CU), ("W", _CU), ("max_iteration", _CU),
+                                                ("fx", C.c_double), ("fy", C.c_double), ("cx", C.c_double), ("cy", C.c_double),
+                                                ("depth_max", C.c_double), ("max_dist", C.c_double), ("relative_fitness", C.c_double),
+                                                ("relative_rmse", C.c_double), ("model_depth", _VP), ("model_normals", _VP),
+                                                ("pose_ref", _VP), ("live", _VP), ("pose_init", _VP), ("result", _VP), ("pose_out", _VP),
+                                                ("partner", _VP), ("workspace", _VP)])
+TRACK_SIGNATURES = {
+    "mipsf_track_workspace_bytes": (_U64, [_I, _U32, _U32, _U32]),
+    "mipsf_track_raycast": (_I, [C.POINTER(TrackRaycastArgs), _P]),
+    "mipsf_track_register": (_I, [C.POINTER(TrackRegisterArgs), _P]),
+}
+
+
 # include/mipsf_image.h (two image stacks compared: error sums, valid-region SSIM and its cs term, the MS-SSIM pyramid's 2 x 2 mean)
 IMAGE_F32, IMAGE_F64 = 0, 1
 IMAGE_WINDOW, IMAGE_TILE_H, IMAGE_TILE_W, IMAGE_MAX_CHANNELS, IMAGE_MAX_SIDE = 11, 16, 32, 4, 8192
@@ -427,7 +451,7 @@ def lib() -> C.CDLL:
                                        + list(COMPACT_SIGNATURES.items()) + list(POSEGRAPH_SIGNATURES.items())
                                        + list(SUBMAP_SIGNATURES.items()) + list(EVAL_SIGNATURES.items())
                                        + list(RASTER_SIGNATURES.items()) + list(TSDF_SIGNATURES.items())
-                                       + list(IMAGE_SIGNATURES.items())):
+                                       + list(IMAGE_SIGNATURES.items()) + list(TRACK_SIGNATURES.items())):
             fn = getattr(handle, name)
             fn.restype = res
             fn.argtypes = args

@@ -9,6 +9,7 @@
 // added in a fixed order: lane -> wave (cross-lane moves) -> block partials in a buffer -> one finishing wave.  The library is
 // built with -ffp-contract=off.
 #include "block_dev.h"
+#include "icp_dev.h"
 #include "icp_grid.h"
 #include "../../include/mipsf_icp.h"
 
@@ -20,8 +21,6 @@ constexpr int WAVES = TPB / MIPSF_WAVE;
 constexpr int SCAN_TILE = GRID_SCAN_TILE; // entries one block scans
 static_assert(SCAN_TILE == TPB * SCAN_ITEMS, "the grid's layout counts the tiles of block_dev.h's scan");
 constexpr int KNN = MIPSF_ICP_KNN;
-constexpr int NSUM = 29;                 // 21 (upper triangle of J^T J) + 6 (J^T r) + pairs + sum of squared distances
-constexpr int NSUM_PAD = 32;
 
 // ------------------------------------------------------------------------------------------------ exclusive scan of uint32
 __global__ void __launch_bounds__(TPB) scan_sums_kernel(const uint32_t* in, uint32_t n, uint32_t* bsum) {
@@ -427,13 +426,7 @@ MIPSF_SINGLE_FP32 __global__ void __launch_bounds__(MIPSF_WAVE) normals_kernel(c
 }
 
 // ------------------------------------------------------------------------------------------------ registration
-struct IcpState {
-    double T[16];
-    double U[12];       // the update the next evaluation applies to its points, 3x4
-    double prev_fitness, prev_rmse;
-    uint32_t done, iter;
-};
-
+// IcpState, the sum layout and the finish step: icp_dev.h
 MIPSF_SINGLE_FP32 __global__ void __launch_bounds__(TPB) icp_init_kernel(const float* __restrict__ src, uint32_t n3, double* __restrict__ P,
                                                                          IcpState* st, double* __restrict__ result) {
     const uint32_t i = blockIdx.x * TPB + threadIdx.x;
@@ -479,29 +472,10 @@ MIPSF_SINGLE_FP32 __global__ void __launch_bounds__(TPB) icp_pair_kernel(double*
             const double* nn = normals + (size_t)b.j * 3;
             const double nx = nn[0], ny = nn[1], nz = nn[2];
             const double r = (((px - (double)b.x) * nx + (py - (double)b.y) * ny) + (pz - (double)b.z) * nz);
-            const double J[6] = {py * nz - pz * ny, pz * nx - px * nz, px * ny - py * nx, nx, ny, nz};
-            int k = 0;
-#pragma unroll
-            for (int a = 0; a < 6; ++a)
-#pragma unroll
-                for (int bb = a; bb < 6; ++bb) c[k++] = J[a] * J[bb];
-#pragma unroll
-            for (int a = 0; a < 6; ++a) c[21 + a] = J[a] * r;
-            c[27] = 1.0;
-            c[28] = b.d2;
+            icp_pair_sums(c, px, py, pz, nx, ny, nz, r, b.d2);
         }
     }
-#pragma unroll
-    for (int k = 0; k < NSUM; ++k) {
-        const double v = wave_sum_d(c[k]);
-        if ((threadIdx.x & 63) == 0) sm[threadIdx.x >> 6][k] = v;
-    }
-    __syncthreads();
-    if (threadIdx.x < NSUM) {
-        double v = sm[0][threadIdx.x];
-        for (int w = 1; w < WAVES; ++w) v += sm[w][threadIdx.x];
-        partial[(size_t)blockIdx.x * NSUM_PAD + threadIdx.x] = v;
-    }
+    icp_block_sums<WAVES, NSUM>(c, sm, partial);
 }
 
 // One wave: add the partials in index order, judge the evaluation, and -- unless it was the last -- solve for the next update.
@@ -509,80 +483,7 @@ MIPSF_SINGLE_FP32 __global__ void __launch_bounds__(MIPSF_WAVE) icp_finish_kerne
                                                                                   IcpState* st, uint32_t max_iteration, double rel_fitness,
                                                                                   double rel_rmse, double* __restrict__ result) {
     if (st->done) return;
-    __shared__ double S[NSUM_PAD];
-    __shared__ double A[6][6];
-    __shared__ double x[6];
-    if (threadIdx.x < NSUM) {
-        double s = 0.0;
-        for (uint32_t b = 0; b < nb; ++b) s += partial[(size_t)b * NSUM_PAD + threadIdx.x];
-        S[threadIdx.x] = s;
-    }
-    __syncthreads();
-    if (threadIdx.x != 0) return;
-    const double pairs = S[27];
-    const double fitness = n_source ? pairs / (double)n_source : 0.0;
-    const double rmse = pairs > 0.0 ? sqrt(S[28] / pairs) : 0.0;
-    const uint32_t iter = st->iter;
-    bool stop = iter >= max_iteration;
-    if (iter > 0 && fabs(st->prev_fitness - fitness) < rel_fitness && fabs(st->prev_rmse - rmse) < rel_rmse) stop = true;
-    for (int j = 0; j < 16; ++j) result[j] = st->T[j];
-    result[16] = pairs, result[17] = fitness, result[18] = rmse, result[19] = (double)iter;
-    if (stop) {
-        st->done = 1u;
-        return;
-    }
-    // J^T J x = -J^T r by Cholesky; no pairs, a pivot that is not above 1e-12 of its diagonal entry (a system without full rank,
-    // whatever the rounding made of it) or a solution that is not finite: no update
-    bool ok = pairs > 0.0;
-    if (ok) {
-        int k = 0;
-        for (int a = 0; a < 6; ++a)
-            for (int b = a; b < 6; ++b) A[a][b] = A[b][a] = S[k++];
-        for (int j = 0; j < 6 && ok; ++j) {
-            const double diag = A[j][j];
-            double d = diag;
-            for (int m = 0; m < j; ++m) d -= A[j][m] * A[j][m];
-            ok = d > 0.0 && d > 1.0e-12 * diag;
-            if (!ok) break;
-            d = sqrt(d);
-            A[j][j] = d;
-            for (int r = j + 1; r < 6; ++r) {
-                double v = A[r][j];
-                for (int m = 0; m < j; ++m) v -= A[r][m] * A[j][m];
-                A[r][j] = v / d;
-            }
-        }
-    }
-    if (ok) {
-        for (int r = 0; r < 6; ++r) {
-            double v = -S[21 + r];
-            for (int m = 0; m < r; ++m) v -= A[r][m] * x[m];
-            x[r] = v / A[r][r];
-        }
-        for (int r = 5; r >= 0; --r) {
-            double v = x[r];
-            for (int m = r + 1; m < 6; ++m) v -= A[m][r] * x[m];
-            x[r] = v / A[r][r];
-        }
-        for (int r = 0; r < 6; ++r) ok = ok && fabs(x[r]) < INFINITY;
-    }
-    double U[12] = {1.0, 0.0, 0.0, 0.0, 0.0, 1.0, 0.0, 0.0, 0.0, 0.0, 1.0, 0.0};
-    if (ok) {       // R = Rz(x2) Ry(x1) Rx(x0)
-        const double sa = sin(x[0]), ca = cos(x[0]), sb = sin(x[1]), cb = cos(x[1]), sc = sin(x[2]), cc = cos(x[2]);
-        U[0] = cc * cb, U[1] = cc * sb * sa - sc * ca, U[2] = cc * sb * ca + sc * sa, U[3] = x[3];
-        U[4] = sc * cb, U[5] = sc * sb * sa + cc * ca, U[6] = sc * sb * ca - cc * sa, U[7] = x[4];
-        U[8] = -sb, U[9] = cb * sa, U[10] = cb * ca, U[11] = x[5];
-    }
-    double Tn[12];
-    for (int r = 0; r < 3; ++r)
-        for (int c = 0; c < 4; ++c) {
-            double v = (U[4 * r] * st->T[c] + U[4 * r + 1] * st->T[4 + c]) + U[4 * r + 2] * st->T[8 + c];
-            if (c == 3) v += U[4 * r + 3];
-            Tn[4 * r + c] = v;
-        }
-    for (int j = 0; j < 12; ++j) st->T[j] = Tn[j], st->U[j] = U[j];
-    st->prev_fitness = fitness, st->prev_rmse = rmse;
-    st->iter = iter + 1u;
+    icp_finish<NSUM>(partial, nb, n_source, st, max_iteration, rel_fitness, rel_rmse, result);
 }
 
 struct RegLayout {
@@ -596,7 +497,6 @@ RegLayout reg_layout(uint32_t n_source) {
     L.bytes = L.partial + (uint64_t)blocks_for(n_source ? n_source : 1, TPB) * NSUM_PAD * sizeof(double);
     return L;
 }
-static_assert(sizeof(IcpState) <= 256, "IcpState");
 
 }  // namespace
 }  // namespace mipsf

@@ -9,7 +9,7 @@
 // wave-uniform index.  The sphere test is the only arithmetic here that the header does not fix: it may be generous, it must
 // never leave out a pair the rule updates.  The projection is stated a second time here, next to raster.hip's.
 #include "block_dev.h"
-#include "../../include/mipsf_tsdf.h"
+#include "tsdf_dev.h"
 
 namespace mipsf {
 namespace {
@@ -208,41 +208,15 @@ MIPSF_SINGLE_FP32 __global__ void __launch_bounds__(TPB) tsdf_integrate_kernel(V
 }
 
 // ------------------------------------------------------------------------------------------------ colour of marched vertices
-struct Axis {
-    uint32_t i0, i1;
-    double f;
-};
-__device__ __forceinline__ Axis axis_of(double x, uint32_t D) {
-    if (D < 2) return Axis{0u, 0u, fmin(fmax(x, 0.0), 1.0)};
-    const double i0 = fmin(fmax(floor(x), 0.0), (double)(D - 2));
-    return Axis{(uint32_t)i0, (uint32_t)i0 + 1u, fmin(fmax(x - i0, 0.0), 1.0)};
-}
-
+// the rule itself: tsdf_dev.h (tsdf_track.hip colours its hits with it)
 MIPSF_SINGLE_FP32 __global__ void __launch_bounds__(TPB) tsdf_sample_kernel(const double* __restrict__ points, uint32_t m, uint32_t X, uint32_t Y,
                                                                             uint32_t Z, const float* __restrict__ weight,
                                                                             const float* __restrict__ color, float* __restrict__ out) {
     const uint32_t p = blockIdx.x * TPB + threadIdx.x;
     if (p >= m) return;
     const double x = points[(size_t)p * 3], y = points[(size_t)p * 3 + 1], z = points[(size_t)p * 3 + 2];
-    float res[3] = {0.0f, 0.0f, 0.0f};
-    if (fabs(x) < INFINITY && fabs(y) < INFINITY && fabs(z) < INFINITY) {
-        const Axis ax = axis_of(x, X), ay = axis_of(y, Y), az = axis_of(z, Z);
-        double den = 0.0, num[3] = {0.0, 0.0, 0.0};
-#pragma unroll
-        for (int corner = 0; corner < 8; ++corner) {
-            const bool a = corner & 4, b = corner & 2, c = corner & 1;
-            const double share = ((a ? ax.f : 1.0 - ax.f) * (b ? ay.f : 1.0 - ay.f)) * (c ? az.f : 1.0 - az.f);
-            const size_t idx = ((size_t)(a ? ax.i1 : ax.i0) * Y + (b ? ay.i1 : ay.i0)) * Z + (c ? az.i1 : az.i0);
-            const double mshare = weight[idx] > 0.0f ? share : 0.0;
-            den = den + mshare;
-#pragma unroll
-            for (int ch = 0; ch < 3; ++ch) num[ch] = num[ch] + mshare * (double)color[idx * 3 + ch];
-        }
-        if (den > 0.0) {
-#pragma unroll
-            for (int ch = 0; ch < 3; ++ch) res[ch] = (float)(num[ch] / den);
-        }
-    }
+    float res[3];
+    tsdf_sample_color(x, y, z, X, Y, Z, weight, color, res);
 #pragma unroll
     for (int ch = 0; ch < 3; ++ch) out[(size_t)p * 3 + ch] = res[ch];
 }

@@ -4,7 +4,10 @@ poses, TSDF-fuse the images, march), the classical baseline (fuse the sensor dep
 that has none.  Upstream fuses with a host library; here it is the kernel of ``csrc/tsdf.hip`` (C ABI: include/mipsf_tsdf.h;
 DESIGN.md 4.19):
 
-    TSDFVolume                 the state (tsdf, weight, optionally colour, all on the device) and integrate / volume / extract_mesh
+    TSDFVolume                 the state (tsdf, weight, optionally colour, all on the device) and integrate / volume / extract_mesh,
+                               raycast (the volume as depth, normal and colour images) and track (a depth frame registered
+                               against such images); kernels of ``csrc/tsdf_track.hip``, C ABI include/mipsf_track.h, DESIGN.md 4.21
+    tsdf_odometry              depth frames -> poses: every frame registered against the ray cast of the volume, then fused
     tsdf_mesh_from_frames      depth frames + poses -> mesh.Mesh
     mesh_from_rendered_depth   model + poses -> rendered depth -> mesh.Mesh
 
@@ -29,6 +32,22 @@ from .scene_mesh import _intrinsics
 class TSDFCounts(NamedTuple):
     updates: int                     # (voxel, view) pairs that updated, over the calls of one integrate()
     observed: int                    # voxels whose weight is positive afterwards
+
+
+class Raycast(NamedTuple):
+    depth: torch.Tensor              # fp32 [n,H,W], z-depth, 0 = no hit
+    normals: Optional[torch.Tensor]  # fp32 [n,H,W,3], world frame, into free space, 0 0 0 = none
+    color: Optional[torch.Tensor]    # fp32 [n,H,W,3]
+    hits: torch.Tensor               # int64 [2] on the device: pixels with a depth, bricks marked
+
+
+class TrackResult(NamedTuple):
+    pose: torch.Tensor               # fp32 [4,4], camera to world
+    transformation: torch.Tensor     # float64 [4,4], the same before its rounding
+    n_correspondences: int
+    fitness: float                   # pairs over the usable live pixels
+    inlier_rmse: float
+    iterations: int
 
 
 def _device(device=None) -> torch.device:
@@ -80,6 +99,7 @@ class TSDFVolume:
             self.tsdf = torch.zeros(self.dims, dtype=torch.float32, device=self.device)
             self.weight = torch.zeros(self.dims, dtype=torch.float32, device=self.device)
             self.color = torch.zeros(self.dims + (3,), dtype=torch.float32, device=self.device) if color else None
+        self._marks = None                   # the ray cast's brick marks (workspace of mipsf_track_raycast), made at the first cast
 
     def reset(self) -> None:
         for t in (self.tsdf, self.weight, self.color):
@@ -126,7 +146,98 @@ class TSDFVolume:
             _lib.check(_lib.lib().mipsf_tsdf_sample(C.byref(a), _lib.stream_ptr()), "tsdf_sample")
         return out
 
+    def raycast_enqueue(self, poses: torch.Tensor, K, H: int, W: int, near: float = 0.0, far: float = math.inf, step: Optional[float] = None,
+                        min_weight: float = 1.0, normals: bool = True, color: bool = False, flags: int = 0) -> Raycast:
+        """mipsf_track_raycast; nothing is read back.  poses fp32 [n,4,4] on the device -> Raycast of device tensors"""
+        _lib.dptr(poses)
+        if poses.dim() != 3 or tuple(poses.shape[1:]) != (4, 4):
+            raise ValueError(f"poses: expected [n,4,4], got {tuple(poses.shape)}")
+        if color and self.color is None:
+            raise ValueError("the volume was made without colour")
+        fx, fy, cx, cy = (float(x) for x in _intrinsics(K))
+        n, H, W = poses.shape[0], int(H), int(W)
+        lib = _lib.lib()
+        size = int(lib.mipsf_track_workspace_bytes(_lib.TRACK_WS_RAYCAST, *self.dims))
+        if size == 0:
+            raise ValueError(f"a volume of {self.dims} cannot be ray cast")
+        with torch.cuda.device(self.device):
+            if self._marks is None or self._marks.numel() < size:
+                self._marks = torch.empty(size, dtype=torch.uint8, device=self.device)
+            depth = torch.empty(n, H, W, dtype=torch.float32, device=self.device)
+            nrm = torch.empty(n, H, W, 3, dtype=torch.float32, device=self.device) if normals else None
+            col = torch.empty(n, H, W, 3, dtype=torch.float32, device=self.device) if color else None
+            record = torch.empty(_lib.TRACK_RECORD_WORDS, dtype=torch.int64, device=self.device)
+            a = _lib.TrackRaycastArgs.new(X=self.dims[0], Y=self.dims[1], Z=self.dims[2], n=n, H=H, W=W, flags=int(flags), voxel=self.voxel_size,
+                                          trunc=self.trunc, fx=fx, fy=fy, cx=cx, cy=cy, near=float(near), far=float(far),
+                                          step=0.5 * self.trunc if step is None else float(step), min_weight=float(min_weight),
+                                          tsdf=_lib.dptr(self.tsdf), weight=_lib.dptr(self.weight),
+                                          color=_lib.dptr(self.color) if color else None, poses=poses.data_ptr() if n else None,
+                                          depth=depth.data_ptr() if n else None, normals=nrm.data_ptr() if normals and n else None,
+                                          color_out=col.data_ptr() if color and n else None, record=_lib.dptr(record, torch.int64),
+                                          workspace=self._marks.data_ptr())
+            for d in range(3):
+                a.origin[d] = float(self.origin[d])
+            _lib.check(lib.mipsf_track_raycast(C.byref(a), _lib.stream_ptr()), "track_raycast")
+        return Raycast(depth, nrm, col, record)
+
+    def track_enqueue(self, depth: torch.Tensor, K, pose_init: torch.Tensor, pose_ref: Optional[torch.Tensor] = None,
+                      model: Optional[Raycast] = None, max_dist: Optional[float] = None, max_iteration: int = 30,
+                      relative_fitness: float = 1e-6, relative_rmse: float = 1e-6, depth_max: float = math.inf, partner: bool = False,
+                      **raycast_kw):
+        """The ray cast from pose_ref (unless ``model`` is given) and mipsf_track_register; nothing is read back.  depth fp32 [H,W],
+        pose_init and pose_ref fp32 [4,4], all on the device -> (result float64 [20]: T row major, correspondences, fitness, inlier
+        rmse, iterations; pose fp32 [4,4]) on the device (, partner int32 [H,W])"""
+        _lib.dptr(depth), _lib.dptr(pose_init), _lib.dptr(pose_ref)
+        pose_ref = pose_init if pose_ref is None else pose_ref
+        if depth.dim() != 2 or tuple(pose_init.shape) != (4, 4) or tuple(pose_ref.shape) != (4, 4):
+            raise ValueError(f"expected depth [H,W] and poses [4,4], got {tuple(depth.shape)}, {tuple(pose_init.shape)}, {tuple(pose_ref.shape)}")
+        H, W = depth.shape
+        fx, fy, cx, cy = (float(x) for x in _intrinsics(K))
+        if model is None:
+            model = self.raycast_enqueue(pose_ref[None], K, H, W, **raycast_kw)
+        if model.normals is None or tuple(model.depth.shape[-2:]) != (H, W) or model.depth.numel() != H * W:
+            raise ValueError("model: one ray-cast view with normals, of the live frame's size")
+        lib = _lib.lib()
+        with torch.cuda.device(self.device):
+            ws = torch.empty(int(lib.mipsf_track_workspace_bytes(_lib.TRACK_WS_REGISTER, H, W, 0)), dtype=torch.uint8, device=self.device)
+            result = torch.empty(_lib.TRACK_RESULT_DOUBLES, dtype=torch.float64, device=self.device)
+            pose = torch.empty(4, 4, dtype=torch.float32, device=self.device)
+            mates = torch.empty(H, W, dtype=torch.int32, device=self.device) if partner else None
+            a = _lib.TrackRegisterArgs.new(H=H, W=W, max_iteration=int(max_iteration), fx=fx, fy=fy, cx=cx, cy=cy, depth_max=float(depth_max),
+                                           max_dist=self.trunc if max_dist is None else float(max_dist),
+                                           relative_fitness=float(relative_fitness), relative_rmse=float(relative_rmse),
+                                           model_depth=_lib.dptr(model.depth), model_normals=_lib.dptr(model.normals),
+                                           pose_ref=pose_ref.data_ptr(), live=depth.data_ptr(), pose_init=pose_init.data_ptr(),
+                                           result=result.data_ptr(), pose_out=pose.data_ptr(),
+                                           partner=_lib.dptr(mates, torch.int32), workspace=ws.data_ptr())
+            _lib.check(lib.mipsf_track_register(C.byref(a), _lib.stream_ptr()), "track_register")
+        return (result, pose, mates) if partner else (result, pose)
+
     # ----------------------------------------------------------------------------------------------------------- public
+    def raycast(self, c2w, K, H: int, W: int, near: float = 0.0, far: float = math.inf, step: Optional[float] = None,
+                min_weight: float = 1.0, normals: bool = True, color: bool = False) -> Raycast:
+        """The volume seen from ``c2w`` ([n,4,4] or [4,4], camera to world, OpenGL convention): z-depth (0 = no surface), world
+        normals pointing into free space and colour per pixel, by marching every pixel's ray through the volume in steps of
+        ``step`` metres (trunc/2 by default) to the first crossing from positive to non-positive tsdf among voxels of weight
+        >= min_weight.  Device tensors; nothing is read back."""
+        with torch.cuda.device(self.device):
+            return self.raycast_enqueue(_poses(c2w, self.device), K, H, W, near, far, step, min_weight, normals, color)
+
+    def track(self, depth, K, pose_init, pose_ref=None, model: Optional[Raycast] = None, max_dist: Optional[float] = None,
+              max_iteration: int = 30, relative_fitness: float = 1e-6, relative_rmse: float = 1e-6, depth_max: float = math.inf) -> TrackResult:
+        """The pose of the depth frame ``depth`` [H,W] by point-to-plane ICP against the volume's ray cast from ``pose_ref`` (by
+        default ``pose_init``; or against ``model``, a one-view Raycast made from pose_ref), starting at ``pose_init``.  Pairs are
+        found by projecting the live points into the model image and kept within ``max_dist`` (trunc by default).  No pyramid:
+        the capture range is a few centimetres and degrees.  One read-back."""
+        with torch.cuda.device(self.device):
+            D = _images(depth, self.device, 0, "depth")[0]
+            P0 = _poses(pose_init, self.device)[0].contiguous()
+            Pr = None if pose_ref is None else _poses(pose_ref, self.device)[0].contiguous()
+            result, pose = self.track_enqueue(D, K, P0, Pr, model, max_dist, max_iteration, relative_fitness, relative_rmse, depth_max)
+            got = torch.cat([result, pose.reshape(-1).to(torch.float64)]).cpu()
+        r = got[:20]
+        return TrackResult(got[20:].reshape(4, 4).to(torch.float32), r[:16].reshape(4, 4).clone(), int(r[16]), float(r[17]), float(r[18]), int(r[19]))
+
     def integrate(self, depth, c2w, K, rgb=None, depth_max: float = math.inf, views_per_call: Optional[int] = None) -> TSDFCounts:
         """Fuses the views in the order given.  depth [n,H,W] or [H,W] (0 = no measurement), c2w [n,4,4] or [4,4] (camera to world,
         the datasets' OpenGL convention), K a 3x3 matrix or (fx, fy, cx, cy), rgb [n,H,W,3] in a colour volume; host or device
@@ -223,6 +334,48 @@ def tsdf_mesh_from_frames(depth, c2w, K, voxel_size: float, trunc: Optional[floa
         vol.integrate(D, P, K, C3, depth_max)
         mesh = vol.extract_mesh(min_weight, mesh_savepath)
     return (mesh, vol) if return_volume else mesh
+
+
+def tsdf_odometry(depth, K, first_pose, voxel_size: float, bounds, trunc: Optional[float] = None, rgb=None, min_correspondences: int = 0,
+                  device=None, **track_kw):
+    """Frame-to-model depth odometry, the classical baseline's tracker: frame 0 is fused at ``first_pose``; every later frame is
+    registered (TSDFVolume.track_enqueue, ``track_kw`` to it) against the ray cast from the previous frame's pose, starting from
+    that pose, and fused at the pose found.  The walk is enqueued whole, the poses handed on between the stages on the device;
+    one read-back at the end.  A frame whose registration ends with fewer than ``min_correspondences`` pairs keeps its initial
+    pose, is not fused (mipsf_tsdf_integrate gets a NaN pose, which updates nothing) and has ``lost`` set in its record.
+    -> (poses fp32 [n,4,4] on the host, records, TSDFVolume); a record is a dict of transformation (float64 [4,4], the
+    registration's pose before its rounding; zero for frame 0), n_correspondences, fitness, inlier_rmse, iterations and lost.
+    Score the poses with ``trajectory_metrics(poses, gt_c2w)`` (aligned ATE); the first pose is given, so ``align=False``
+    measures the drift itself."""
+    voxel_size = float(voxel_size)
+    trunc = 4.0 * voxel_size if trunc is None else float(trunc)
+    dev = depth.device if torch.is_tensor(depth) and depth.is_cuda else _device(device)
+    b = np.asarray(bounds.detach().cpu() if torch.is_tensor(bounds) else bounds, np.float64).reshape(3, 2)
+    dims = [int(c) + 1 for c in np.ceil((b[:, 1] - b[:, 0]) / voxel_size)]
+    with torch.cuda.device(dev):
+        D = _images(depth, dev, 0, "depth")
+        C3 = None if rgb is None else _images(rgb, dev, 3, "rgb")
+        n, H, W = D.shape
+        if n < 1:
+            raise ValueError("no frames")
+        vol = TSDFVolume(b[:, 0], voxel_size, dims, trunc, color=C3 is not None, device=dev)
+        poses = torch.empty(n, 4, 4, dtype=torch.float32, device=dev)
+        results = torch.zeros(n, _lib.TRACK_RESULT_DOUBLES, dtype=torch.float64, device=dev)
+        lost = torch.zeros(n, dtype=torch.bool, device=dev)
+        poses[0] = _poses(first_pose, dev)[0]
+        nan_pose = torch.full((4, 4), math.nan, dtype=torch.float32, device=dev)
+        vol.integrate_enqueue(D[:1], poses[:1], K, None if C3 is None else C3[:1])
+        for k in range(1, n):
+            prev = poses[k - 1]
+            result, pose = vol.track_enqueue(D[k], K, prev, **track_kw)
+            bad = result[16] < float(min_correspondences)
+            poses[k] = torch.where(bad, prev, pose)
+            results[k], lost[k] = result, bad
+            vol.integrate_enqueue(D[k:k + 1], torch.where(bad, nan_pose, pose)[None], K, None if C3 is None else C3[k:k + 1])
+        got = torch.cat([poses.reshape(n, 16).to(torch.float64), results, lost[:, None].to(torch.float64)], 1).cpu()
+    records = [{"transformation": r[16:32].reshape(4, 4).clone(), "n_correspondences": int(r[32]), "fitness": float(r[33]),
+                "inlier_rmse": float(r[34]), "iterations": int(r[35]), "lost": bool(r[36])} for r in got]
+    return got[:, :16].reshape(n, 4, 4).to(torch.float32), records, vol
 
 
 @torch.no_grad()
