@@ -105,9 +105,9 @@ int mipsf_hashgrid_dx_from_jac(const float* jac, const float* dout, float* dx, c
  * dx (nullable) += dL/dx [M,3].  Replaces tcnn's kernel_grid_backward (+ _input) reached through model/encodings.py:14-25.
  *   scratch    MIPSF_SIZE_HASHGRID_BWD_SCRATCH floats owned by the caller
  *   counters   nullable: MIPSF_SIZE_HASHGRID_COUNTER_WORDS uint32 the CALLER keeps between calls (all zero before the first
- *              call; every call leaves the block ready for the next one): one launch fewer -- the routed scatter is then three
- *              launches (route, accumulate, fold of split bins).  One block per stream: calls that share a block must be
- *              ordered.  NULL: the block sits in `scratch` and one more launch clears it
+ *              call; every call leaves the block ready for the next one): one launch fewer -- the routed scatter is then two
+ *              launches (route, accumulate; split bins are folded inside the accumulate launch).  One block per stream:
+ *              calls that share a block must be ordered.  NULL: the block sits in `scratch` and one more launch clears it
  *   flags      MIPSF_HG_DPARAMS_ZERO: the caller vouches that dparams is all zero on entry (the gradient buffer of an optimiser
  *              that clears it, a fresh allocation): table slices are stored instead of read-modify-written.
  *              MIPSF_HG_ROUTED: `scratch` was filled by mipsf_hashgrid_route for this x (the routing third of the call
@@ -151,8 +151,7 @@ typedef struct mipsf_hashgrid_bwd_args {
     uint32_t flags;
 } mipsf_hashgrid_bwd_args;
 int mipsf_hashgrid_bwd(const mipsf_hashgrid_bwd_args* args_host, void* stream);
-int mipsf_hashgrid_route(const float* x, float* scratch, uint32_t M, const mipsf_grid_meta* meta_host, void* stream);
-/* parity probe: idx[(i*L + level)*8 + corner] = entry index inside the level (uint32). */
+int mipsf_hashgrid_route(const float* x, float* scratch, uint32_t M, const mipsf_grid_meta* meta_host, void* stream);/* parity probe: idx[(i*L + level)*8 + corner] = entry index inside the level (uint32). */
 int mipsf_hashgrid_indices(const float* x, uint32_t* idx, uint32_t M, const mipsf_grid_meta* meta_host,
                            void* stream);
 

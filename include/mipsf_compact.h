@@ -34,6 +34,28 @@ int mipsf_decoder_live_compact(const float* dout, uint32_t M, uint32_t* live_lis
 int mipsf_hashgrid_dx_from_jac_list(const float* jac, const float* dout, float* dx, const uint32_t* live_list, uint32_t M,
                                     const mipsf_grid_meta* meta_host, int layout, void* stream);
 
+/* RAY MASK.  `wants_dx`: one uint32 per ray of S consecutive samples; 0 = the gradient of the ray's points reaches no
+ * parameter (its pose is one of the fixed ones), so nobody needs d feat / d x of its samples.
+ *   mipsf_gather_pose_place_fwd_masked   mipsf_gather_pose_place_fwd that also writes the mask: wants_dx[n] = owner[n] >= F
+ *                                        (an owner out of range counts as pose 0, as in mipsf_place_pose_bwd)
+ *   mipsf_hashgrid_fwd_masked            mipsf_hashgrid_fwd; with jac and ray_mask != NULL the Jacobian of a masked ray's
+ *                                        samples is NOT stored (those words of jac keep what they held); out is unchanged
+ *   mipsf_hashgrid_dx_from_jac_masked    mipsf_hashgrid_dx_from_jac (tile_live) / _list (live_list), at most one of the two;
+ *                                        a sample of a masked ray that the call visits gets dx = +0.0f (what was there is
+ *                                        dropped) and neither its Jacobian nor its gradient is read
+ * M must be a multiple of S.  ray_mask == NULL: exactly the unmasked functions. */
+int mipsf_gather_pose_place_fwd_masked(const float* db, uint64_t n_rows, const int64_t* idx, const float* fixed_poses,
+                                       const float* rot, const float* trans, uint32_t F, uint32_t K, const int64_t* owner,
+                                       const float* noise, const float* z_uniform, const float* z_near_offsets,
+                                       const float* z_near_nodepth, const mipsf_render_cfg* cfg_host, float* d_cam, float* rgb,
+                                       float* depth, float* z_vals, float* xn, uint32_t* counts, uint32_t* wants_dx, uint32_t N,
+                                       void* stream);
+int mipsf_hashgrid_fwd_masked(const float* x, const float* params, float* out, float* jac, const uint32_t* ray_mask, uint32_t S,
+                              uint32_t M, const mipsf_grid_meta* meta_host, int layout, void* stream);
+int mipsf_hashgrid_dx_from_jac_masked(const float* jac, const float* dout, float* dx, const uint32_t* tile_live,
+                                      const uint32_t* live_list, const uint32_t* ray_mask, uint32_t S, uint32_t M,
+                                      const mipsf_grid_meta* meta_host, int layout, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -135,8 +135,7 @@ SIGNATURES = {
     "mipsf_hashgrid_fwd": (_I, [_P, _P, _P, _P, _U32, C.POINTER(GridMeta), _I, _P]),
     "mipsf_hashgrid_dx_from_jac": (_I, [_P, _P, _P, _P, _U32, C.POINTER(GridMeta), _I, _P]),
     "mipsf_hashgrid_bwd": (_I, [C.POINTER(HashgridBwdArgs), _P]),
-    "mipsf_hashgrid_route": (_I, [_P, _P, _U32, C.POINTER(GridMeta), _P]),
-    "mipsf_hashgrid_indices": (_I, [_P, _P, _U32, C.POINTER(GridMeta), _P]),
+    "mipsf_hashgrid_route": (_I, [_P, _P, _U32, C.POINTER(GridMeta), _P]),    "mipsf_hashgrid_indices": (_I, [_P, _P, _U32, C.POINTER(GridMeta), _P]),
     "mipsf_freq_fwd": (_I, [_P, _P, _U32, _U32, _U32, _P]),
     "mipsf_freq_bwd": (_I, [_P, _P, _P, _U32, _U32, _U32, _P]),
     "mipsf_decoder_pack": (_I, [C.POINTER(DecoderWeights), _P, _P]),
@@ -189,6 +188,10 @@ McubesWeldArgs = _args("McubesWeldArgs", [("T", _CU), ("soup", _VP), ("scratch",
 COMPACT_SIGNATURES = {
     "mipsf_decoder_live_compact": (_I, [_P, _U32, _P, _P, _P, _I, _P]),
     "mipsf_hashgrid_dx_from_jac_list": (_I, [_P, _P, _P, _P, _U32, C.POINTER(GridMeta), _I, _P]),
+    "mipsf_gather_pose_place_fwd_masked": (_I, [_P, _U64, _P, _P, _P, _P, _U32, _U32, _P, _P, _P, _P, _P, C.POINTER(RenderCfg),
+                                                _P, _P, _P, _P, _P, _P, _P, _U32, _P]),
+    "mipsf_hashgrid_fwd_masked": (_I, [_P, _P, _P, _P, _P, _U32, _U32, C.POINTER(GridMeta), _I, _P]),
+    "mipsf_hashgrid_dx_from_jac_masked": (_I, [_P, _P, _P, _P, _P, _P, _U32, _U32, C.POINTER(GridMeta), _I, _P]),
 }
 
 MESH_SIGNATURES = {
@@ -432,6 +435,16 @@ def buffer_size(which: int, n: int = 0, a: int = 0, b: int = 0, meta=None) -> in
     if v == 0xFFFFFFFFFFFFFFFF:
         raise RuntimeError((lib().mipsf_last_error() or b"mipsf_buffer_size: bad query").decode())
     return int(v)
+
+
+def hashgrid_counter_layout(meta) -> dict:
+    """Word offsets of the routed scatter's counter block (csrc/hashgrid.hip make_plan; tests and probes): {bin counts | queue
+    head + tickets (4) | arrivals | first item | parts}, one word per bin each.  Every word in front of `first` reads zero
+    between calls."""
+    end = buffer_size(SIZE_HASHGRID_COUNTER_WORDS, meta=meta)
+    bins = (end - 4) // 4
+    return {"count": 0, "nitems": bins, "arrive": bins + 4, "first": 2 * bins + 4, "parts": 3 * bins + 4, "end": end,
+            "n_bins": bins}
 
 
 _lib: Optional[C.CDLL] = None

@@ -138,11 +138,19 @@ __device__ __forceinline__ void level_jacobian(const Cell& cell, const float2 (&
 // ------------------------------------------------------------------------------ forward
 // JAC: also store d out / d x of this (sample, level) -- 3 x (d f0/d x_d, d f1/d x_d), planes [L][3][M][2] -- so that
 // the backward gets dL/dx from a streaming pass (hashgrid_dx_jac_kernel) instead of gathering the table again.
+// ray_mask (optional, with JAC): one word per ray of S consecutive samples; 0 = nobody uses d x of this ray (a ray of a pose
+// that is not optimised): its 384 bytes of Jacobian per sample are not stored and stay unwritten -- hashgrid_dx_jac_kernel,
+// given the same mask, does not read them.  With S = 64 a wave is one ray and the test is wave-uniform.
+__device__ __forceinline__ bool ray_wants_dx(const uint32_t* __restrict__ ray_mask, uint32_t S, uint32_t i) {
+    return ray_mask == nullptr || ray_mask[S == 64u ? i >> 6 : i / S] != 0u;
+}
+
 template <int LAYOUT, bool JAC>
 __global__ __launch_bounds__(HG_BLOCK) void hashgrid_fwd_kernel(const float* __restrict__ x,
                                                                 const float2* __restrict__ table,
                                                                 float* __restrict__ out, float* __restrict__ jac,
-                                                                uint32_t M, GridLevels g, uint32_t nchunk) {
+                                                                uint32_t M, GridLevels g, uint32_t nchunk,
+                                                                const uint32_t* __restrict__ ray_mask, uint32_t S) {
     uint32_t chunk;
     const int level = decode_level(g.n_levels, nchunk, chunk);
     if (level >= (int)g.n_levels) return;
@@ -173,7 +181,7 @@ __global__ __launch_bounds__(HG_BLOCK) void hashgrid_fwd_kernel(const float* __r
     typedef float f32x2_t __attribute__((ext_vector_type(2)));
     f32x2_t* dst = reinterpret_cast<f32x2_t*>(out + feat_index<LAYOUT>(i, level, M, g.n_levels));
     __builtin_nontemporal_store(f32x2_t{a0, a1}, dst);
-    if (JAC) {
+    if (JAC && ray_wants_dx(ray_mask, S, i)) {
         // [L][3][M][2]: the three derivative pairs of a (sample, level) go to three planes, each written 8 bytes per
         // lane, contiguous across the wavefront
         f32x2_t* j2 = reinterpret_cast<f32x2_t*>(jac) + (size_t)level * 3 * M + i;
@@ -202,7 +210,8 @@ __global__ __launch_bounds__(HG_BLOCK) void hashgrid_fwd_kernel(const float* __r
 //     per lane-op per CU on gfx950, ds_add_f32 at 3.0 (serialised lane by lane; tools/micro/lds_atomic.hip), and
 //     fp64 sums make the result independent of the arrival order to fp32 precision;
 //   * the slice is added to dparams with coalesced read-modify-writes; bins with several parts go through
-//     partial slices and a reduce kernel.  No global float atomics, no inter-workgroup communication.
+//     partial slices that the workgroup which stores the bin's last one folds, in part order (scatter_item).  No global
+//     float atomics; the only inter-workgroup traffic is one arrival count per part of a split bin, and nobody waits for it.
 constexpr int SC_BLOCK = 1024;                      // threads of an accumulate workgroup
 // Layout of the fp64 slice in LDS.  Interleaved ([entry][2 features], round 1) puts every lane of one ds_add_f64 instruction on
 // an address = 0 (or 8) mod 16: half of the LDS banks never take part, and random entries collide twice as often as they must
@@ -277,8 +286,9 @@ struct ScatterPlan {
     uint32_t max_slice;                           // entries of the largest slice (= the accumulate kernel's LDS / 16)
     uint32_t dense_bins;                          // bins [0, dense_bins) belong to the dense levels (they come first)
     uint32_t fresh;                               // 1: the caller vouches that dparams is all zero on entry: slices are stored, not added
+    uint32_t fold_launch;                         // 1: split bins are folded by hashgrid_scatter_reduce_kernel (MIPSF_SC_FOLD_LAUNCH), not in the accumulate kernel
     // scratch layout, in 4-byte words from the start of the scratch buffer
-    uint32_t w_count, w_first, w_parts, w_nitems, w_items;
+    uint32_t w_count, w_arrive, w_first, w_parts, w_nitems, w_items;
     uint64_t w_records, w_partial, w_end;         // records: n_bins regions of bin_cap words
 };
 
@@ -310,10 +320,11 @@ static ScatterPlan make_plan(const GridLevels& g, uint32_t M) {
     uint64_t w = 0;
     p.w_count = (uint32_t)w, w += bins;
     p.w_nitems = (uint32_t)w, w += 4;
+    p.w_arrive = (uint32_t)w, w += bins;                    // parts of a split bin whose partial slice has been published
     p.w_first = (uint32_t)w, w += bins;
     p.w_parts = (uint32_t)w, w += bins;
     w = (w + 3) / 4 * 4;
-    p.w_items = (uint32_t)w;                                // end of the counter block {counts | head, tickets | first | parts}
+    p.w_items = (uint32_t)w;                                // end of the counter block {counts | head, tickets | arrivals | first | parts}
     w = (w + 15) / 16 * 16;
     p.w_records = w, w += (uint64_t)bins * M;
     w = (w + 15) / 16 * 16;
@@ -701,13 +712,62 @@ __device__ __forceinline__ uint32_t part_of(const ScatterPlan& plan, uint32_t bi
     return bin < plan.dense_bins ? SC_PART_DENSE : SC_PART;
 }
 
+// How a partial slice is published to the workgroup that will fold it.  1: agent-scope (write-through) stores, which are at
+// the device's coherence point once every storing wave has drained them, and no release fence.  0: plain stores, then one
+// lane's agent-scope release fence in front of the arrival count -- the fence writes back whatever the XCD's L2 holds dirty
+// (the other workgroups' table slices), 3 us on the accumulate kernel of the mapping step (73.4 against 70.3 us).
+#ifndef MIPSF_SC_PUBLISH_WT
+#define MIPSF_SC_PUBLISH_WT 1
+#endif
+
+// The fold of a split bin: dparams (+)= the bin's partial slices, summed in part order 0, 1, 2, ... whoever runs it.  Eight
+// parts in flight (a load per iteration was one memory round trip per part: 11 parts on the coarsest levels).  AGENT selects
+// the loads: inside the accumulate kernel the slices were written by other CUs during this launch and this CU's L1 is never
+// refreshed by their stores, so every load is an agent-scope one (it is served by L2); the reduce kernel reads them
+// behind a kernel boundary with plain loads.  The arithmetic is the same in both.
+template <bool AGENT>
+__device__ __forceinline__ float2 fold_entry(const float2* p2, uint32_t parts, float2 cur) {
+    float2 a = make_float2(0.f, 0.f);
+    for (uint32_t q = 0; q < parts; q += 8) {
+        float2 v[8];
+#pragma unroll
+        for (uint32_t k = 0; k < 8; ++k) {
+            v[k] = make_float2(0.f, 0.f);
+            if (q + k < parts) {
+                if (AGENT) {
+                    const unsigned long long u = __hip_atomic_load(
+                        reinterpret_cast<const unsigned long long*>(p2 + (size_t)(q + k) * SC_MAX_SLICE), __ATOMIC_RELAXED,
+                        __HIP_MEMORY_SCOPE_AGENT);
+                    v[k] = make_float2(__uint_as_float((uint32_t)u), __uint_as_float((uint32_t)(u >> 32)));
+                } else {
+                    v[k] = p2[(size_t)(q + k) * SC_MAX_SLICE];
+                }
+            }
+        }
+#pragma unroll
+        for (uint32_t k = 0; k < 8; ++k) a.x += v[k].x, a.y += v[k].y;
+    }
+    cur.x += a.x, cur.y += a.y;
+    return cur;
+}
+
 // One work item = (bin, part of its records): the slice's gradient is accumulated in LDS (fp64) and added to dparams (the
-// bin's only part) or left as a partial slice for the reduce kernel.  desc = {bin | part << 16, records of the bin, parts of
-// the bin}, item_index = position in the item order (names the partial slice).
+// bin's only part) or left as a partial slice.  desc = {bin | part << 16, records of the bin, parts of the bin},
+// item_index = position in the item order (names the partial slice).
+//
+// A split bin is folded HERE, by the workgroup that publishes its last partial slice (unless plan.fold_launch leaves it to
+// hashgrid_scatter_reduce_kernel): the dense items lead the order, so a dense bin's last part is through tens of
+// microseconds before the kernel ends and the fold replaces a launch and its two memory round trips.  Publishing = the
+// slice goes out with agent-scope stores (MIPSF_SC_PUBLISH_WT), every wave drains its stores, and behind the barrier ONE
+// lane adds 1 to the bin's arrival counter (cw, w_arrive) at agent scope; the workgroup that reads parts - 1 back is the
+// last one: it acquires at agent scope, folds in part order with agent-scope loads (so the sum does not depend on who
+// folds) and puts the counter back to zero.  Nobody waits for a counter; a workgroup that is not the last one takes its
+// next item.  sh_flag: one LDS word that is free during the item loop.
 template <int LAYOUT>
 __device__ __forceinline__ void scatter_item(const float* __restrict__ x, const float* __restrict__ dout,
                                              float* __restrict__ dparams, uint32_t M, const GridLevels& g,
-                                             const ScatterPlan& plan, uint32_t* __restrict__ ws, double* __restrict__ acc,
+                                             const ScatterPlan& plan, uint32_t* __restrict__ ws, uint32_t* __restrict__ cw,
+                                             uint32_t* sh_flag, double* __restrict__ acc,
                                              const uint4 desc, const uint32_t item_index) {
     const uint32_t item = desc.x;
     const uint32_t sc_plane1 = plan.max_slice;
@@ -967,12 +1027,47 @@ __device__ __forceinline__ void scatter_item(const float* __restrict__ x, const 
             }
         }
     } else {
-        float2* pdst = reinterpret_cast<float2*>(reinterpret_cast<float*>(ws) + plan.w_partial) +
-                       (size_t)item_index * SC_MAX_SLICE;
+        float2* part0 = reinterpret_cast<float2*>(reinterpret_cast<float*>(ws) + plan.w_partial);
+        float2* pdst = part0 + (size_t)item_index * SC_MAX_SLICE;
+        if (plan.fold_launch) {
+            for (uint32_t e = threadIdx.x; e < count; e += SC_BLOCK) {
+                const double2 a = a2(e);
+                pdst[e] = make_float2((float)a.x, (float)a.y);
+            }
+            return;
+        }
         for (uint32_t e = threadIdx.x; e < count; e += SC_BLOCK) {
             const double2 a = a2(e);
+#if MIPSF_SC_PUBLISH_WT
+            __hip_atomic_store(reinterpret_cast<unsigned long long*>(pdst + e),
+                               (unsigned long long)__float_as_uint((float)a.x) | ((unsigned long long)__float_as_uint((float)a.y) << 32),
+                               __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+#else
             pdst[e] = make_float2((float)a.x, (float)a.y);
+#endif
         }
+        // publish: every storing wave drains, the barrier collects them, one lane (releases and) counts
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        __syncthreads();
+        if (threadIdx.x == 0) {
+#if !MIPSF_SC_PUBLISH_WT
+            __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
+            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");     // (the write-back is through before the counter moves)
+#endif
+            const uint32_t before = __hip_atomic_fetch_add(&cw[plan.w_arrive + bin], 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            const bool last = before == desc.z - 1u;
+            if (last) {
+                __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
+                asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); // (the invalidate is through before the barrier lets the others load)
+            }
+            *sh_flag = last ? 1u : 0u;
+        }
+        __syncthreads();
+        if (*sh_flag == 0u) return;
+        const float2* p2 = part0 + (size_t)(item_index - part) * SC_MAX_SLICE;     // (a bin's items are consecutive)
+        for (uint32_t e = threadIdx.x; e < count; e += SC_BLOCK)
+            dst[e] = fold_entry<true>(p2 + e, desc.z, plan.fresh ? make_float2(0.f, 0.f) : dst[e]);
+        if (threadIdx.x == 0) __hip_atomic_store(&cw[plan.w_arrive + bin], 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     }
 }
 
@@ -984,12 +1079,14 @@ __device__ __forceinline__ void scatter_item(const float* __restrict__ x, const 
 //       most of which found an "unused" mark, cleared 160 KB of LDS for nothing and left;
 //   (2) pulls items from ONE device-scope counter (dense levels first: the long items lead, as in LPT scheduling) until the
 //       order is exhausted -- no static assignment of items to workgroups, the tail is as short as the last item.
-// cw = the small counter block: {bin counts | head, ticket A, ticket B, - | first item of every bin | parts of every bin}.
-// On entry the counts are the routing kernel's and head / tickets are zero; on exit everything but first / parts is zero
-// again (those two are rewritten for EVERY bin by every call), so a caller that keeps the block between calls never
-// launches a clearing kernel.  Nobody waits for a ticket: the LAST workgroup through a point does the clearing --
+// cw = the small counter block: {bin counts | head, ticket A, ticket B, - | arrivals of every bin | first item of every bin |
+// parts of every bin}.  On entry the counts are the routing kernel's and head / tickets / arrivals are zero; on exit
+// everything but first / parts is zero again (those two are rewritten for EVERY bin by every call), so a caller that keeps
+// the block between calls never launches a clearing kernel.  Nobody waits for a ticket: the LAST workgroup through a point
+// does the clearing --
 //   ticket A (after the prologue: every workgroup has read the counts)   -> the counts are cleared,
-//   ticket B (after the loop: every workgroup has made its last pull)    -> head and both tickets are cleared.
+//   ticket B (after the loop: every workgroup has made its last pull)    -> head and both tickets are cleared,
+//   arrivals of a split bin (scatter_item: its last partial slice is out) -> the bin is folded, its arrivals are cleared.
 template <int LAYOUT>
 __global__ __launch_bounds__(SC_BLOCK) void hashgrid_scatter_persist_kernel(const float* __restrict__ x,
                                                                            const float* __restrict__ dout,
@@ -1068,7 +1165,7 @@ __global__ __launch_bounds__(SC_BLOCK) void hashgrid_scatter_persist_kernel(cons
 #ifdef MIPSF_SC_TRACE    // tools/probe_scatter_trace.py: one row per item {item, bin | part << 16, records, begin, end (10 ns ticks), XCC, workgroup}
         const uint64_t tr_t0 = wall_clock64();
 #endif
-        scatter_item<LAYOUT>(x, dout, dparams, M, g, plan, ws, acc, desc, i);
+        scatter_item<LAYOUT>(x, dout, dparams, M, g, plan, ws, cw, &wtot[0], acc, desc, i);    // (wtot: free since the prologue)
 #ifdef MIPSF_SC_TRACE
         __syncthreads();
         if (t == 0) {
@@ -1090,7 +1187,8 @@ __global__ __launch_bounds__(SC_BLOCK) void hashgrid_scatter_persist_kernel(cons
     }
 }
 
-// folds the partial slices of bins that were split over several workgroups into dparams
+// folds the partial slices of bins that were split over several workgroups into dparams: a launch of its own, only with
+// MIPSF_SC_FOLD_LAUNCH=1 (A/B against the fold inside the accumulate kernel, scatter_item)
 __global__ __launch_bounds__(256) void hashgrid_scatter_reduce_kernel(float* __restrict__ dparams, GridLevels g,
                                                                       ScatterPlan plan, const uint32_t* __restrict__ ws,
                                                                       const uint32_t* __restrict__ cw) {
@@ -1108,19 +1206,7 @@ __global__ __launch_bounds__(256) void hashgrid_scatter_reduce_kernel(float* __r
     const float2* p2 = reinterpret_cast<const float2*>(reinterpret_cast<const float*>(ws) + plan.w_partial) +
                        (size_t)cw[plan.w_first + bin] * SC_MAX_SLICE + e;
     float2* d = reinterpret_cast<float2*>(dparams) + g.offsets[level] + begin + e;
-    float2 cur = plan.fresh ? make_float2(0.f, 0.f) : *d;
-    // eight partial slices in flight (a load per iteration was one memory round trip per part: 11 parts on the coarsest
-    // levels, 10 us for 10 MB); the sum keeps the order part 0, 1, 2, ...
-    float2 a = make_float2(0.f, 0.f);
-    for (uint32_t q = 0; q < parts; q += 8) {
-        float2 v[8];
-#pragma unroll
-        for (uint32_t k = 0; k < 8; ++k) v[k] = q + k < parts ? p2[(size_t)(q + k) * SC_MAX_SLICE] : make_float2(0.f, 0.f);
-#pragma unroll
-        for (uint32_t k = 0; k < 8; ++k) a.x += v[k].x, a.y += v[k].y;
-    }
-    cur.x += a.x, cur.y += a.y;
-    *d = cur;
+    *d = fold_entry<false>(p2, parts, plan.fresh ? make_float2(0.f, 0.f) : *d);
 }
 
 // dL/dx of one level per thread (tcnn kernel_grid_backward_input); written to per-level partials, no atomics
@@ -1173,12 +1259,15 @@ __global__ __launch_bounds__(256) void hashgrid_dx_reduce_kernel(const float* __
 // works on sample 32 * tile(t / 32) + t % 32 of the listed tiles only: the others have a zero feature gradient, add
 // nothing, and their 384 bytes of Jacobian per sample stay unread.
 // live_list (optional, instead of tiles): the live-sample list of mipsf_decoder_live_compact; thread t works on its t-th entry.
+// ray_mask (optional; S samples per ray): the mask the forward was given.  A sample of a ray with a zero word gets d x = +0
+// -- whatever the decoder's backward left there is dropped with it -- and neither its Jacobian nor its d feat is loaded.
 template <int LAYOUT>
 MIPSF_SINGLE_FP32 __global__ __launch_bounds__(256) void hashgrid_dx_jac_kernel(const float* __restrict__ jac,
                                                               const float* __restrict__ dout, float* __restrict__ dx,
                                                               uint32_t M, uint32_t L,
                                                               const uint32_t* __restrict__ tiles,
-                                                              const uint32_t* __restrict__ live_list) {
+                                                              const uint32_t* __restrict__ live_list,
+                                                              const uint32_t* __restrict__ ray_mask, uint32_t S) {
     uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
     if (live_list != nullptr) {
         if (i >= M || i >= live_list[0]) return;
@@ -1197,6 +1286,10 @@ MIPSF_SINGLE_FP32 __global__ __launch_bounds__(256) void hashgrid_dx_jac_kernel(
         i = tiles[mipsf::dl::TL_HEADER + q * cap + (k - first)] * 32u + (i & 31u);
     }
     if (i >= M) return;
+    if (!ray_wants_dx(ray_mask, S, i)) {
+        dx[3 * (size_t)i] = 0.f, dx[3 * (size_t)i + 1] = 0.f, dx[3 * (size_t)i + 2] = 0.f;
+        return;
+    }
     float a[3] = {0.f, 0.f, 0.f};
     for (uint32_t l = 0; l < L; ++l) {
         const float2* j2 = reinterpret_cast<const float2*>(jac) + (size_t)l * 3 * M + i;      // [L][3][M][2]
@@ -1580,18 +1673,25 @@ using namespace mipsf;
 
 extern "C" {
 
+static int check_ray_mask(const uint32_t* ray_mask, uint32_t S, uint32_t M) {
+    MIPSF_REQUIRE(ray_mask == nullptr || (S >= 1 && M % S == 0), "ray mask: %u samples are not whole rays of %u", M, S);
+    return 0;
+}
+
 static int hashgrid_fwd_impl(const float* x, const float* params, float* out, float* jac, uint32_t M,
-                             const mipsf_grid_meta* meta, int layout, void* stream) {
+                             const mipsf_grid_meta* meta, int layout, void* stream, const uint32_t* ray_mask = nullptr,
+                             uint32_t S = 0) {
     GridLevels g;
     if (int rc = to_levels(meta, g)) return rc;
     if (M == 0) return 0;
     MIPSF_REQUIRE(x && params && out, "null pointer");
     MIPSF_REQUIRE(layout == MIPSF_FEAT_AOS || layout == MIPSF_FEAT_LEVEL_MAJOR, "bad layout %d", layout);
+    if (int rc = check_ray_mask(ray_mask, S, M)) return rc;
     uint32_t nchunk;
     const uint32_t nb = grid_blocks(M, g.n_levels, nchunk);
     hipStream_t s = (hipStream_t)stream;
     const float2* table = reinterpret_cast<const float2*>(params);
-#define FWD(LAY, J) hipLaunchKernelGGL((hashgrid_fwd_kernel<LAY, J>), dim3(nb), dim3(HG_BLOCK), 0, s, x, table, out, jac, M, g, nchunk)
+#define FWD(LAY, J) hipLaunchKernelGGL((hashgrid_fwd_kernel<LAY, J>), dim3(nb), dim3(HG_BLOCK), 0, s, x, table, out, jac, M, g, nchunk, ray_mask, S)
     if (layout == MIPSF_FEAT_AOS) { if (jac) FWD(MIPSF_FEAT_AOS, true); else FWD(MIPSF_FEAT_AOS, false); }
     else { if (jac) FWD(MIPSF_FEAT_LEVEL_MAJOR, true); else FWD(MIPSF_FEAT_LEVEL_MAJOR, false); }
 #undef FWD
@@ -1602,20 +1702,31 @@ int mipsf_hashgrid_fwd(const float* x, const float* params, float* out, float* j
                        const mipsf_grid_meta* meta, int layout, void* stream) {
     return hashgrid_fwd_impl(x, params, out, jac, M, meta, layout, stream);
 }
+int mipsf_hashgrid_fwd_masked(const float* x, const float* params, float* out, float* jac, const uint32_t* ray_mask, uint32_t S,
+                              uint32_t M, const mipsf_grid_meta* meta, int layout, void* stream) {
+    return hashgrid_fwd_impl(x, params, out, jac, M, meta, layout, stream, ray_mask, S);
+}
 
 static int dx_from_jac(const float* jac, const float* dout, float* dx, const uint32_t* tile_live, const uint32_t* live_list, uint32_t M,
-                       const mipsf_grid_meta* meta, int layout, void* stream) {
+                       const mipsf_grid_meta* meta, int layout, void* stream, const uint32_t* ray_mask = nullptr, uint32_t S = 0) {
     GridLevels g;
     if (int rc = to_levels(meta, g)) return rc;
     if (M == 0) return 0;
     MIPSF_REQUIRE(jac && dout && dx, "null pointer");
     MIPSF_REQUIRE(layout == MIPSF_FEAT_AOS || layout == MIPSF_FEAT_LEVEL_MAJOR, "bad layout %d", layout);
+    MIPSF_REQUIRE(!(tile_live && live_list), "tile_live and live_list are alternatives");
+    if (int rc = check_ray_mask(ray_mask, S, M)) return rc;
     hipStream_t s = (hipStream_t)stream;
     if (layout == MIPSF_FEAT_AOS)
-        hipLaunchKernelGGL(hashgrid_dx_jac_kernel<MIPSF_FEAT_AOS>, dim3((M + 255) / 256), dim3(256), 0, s, jac, dout, dx, M, g.n_levels, tile_live, live_list);
+        hipLaunchKernelGGL(hashgrid_dx_jac_kernel<MIPSF_FEAT_AOS>, dim3((M + 255) / 256), dim3(256), 0, s, jac, dout, dx, M, g.n_levels, tile_live, live_list, ray_mask, S);
     else
-        hipLaunchKernelGGL(hashgrid_dx_jac_kernel<MIPSF_FEAT_LEVEL_MAJOR>, dim3((M + 255) / 256), dim3(256), 0, s, jac, dout, dx, M, g.n_levels, tile_live, live_list);
+        hipLaunchKernelGGL(hashgrid_dx_jac_kernel<MIPSF_FEAT_LEVEL_MAJOR>, dim3((M + 255) / 256), dim3(256), 0, s, jac, dout, dx, M, g.n_levels, tile_live, live_list, ray_mask, S);
     return check_launch("hashgrid_dx_from_jac");
+}
+int mipsf_hashgrid_dx_from_jac_masked(const float* jac, const float* dout, float* dx, const uint32_t* tile_live,
+                                      const uint32_t* live_list, const uint32_t* ray_mask, uint32_t S, uint32_t M,
+                                      const mipsf_grid_meta* meta, int layout, void* stream) {
+    return dx_from_jac(jac, dout, dx, tile_live, live_list, M, meta, layout, stream, ray_mask, S);
 }
 int mipsf_hashgrid_dx_from_jac(const float* jac, const float* dout, float* dx, const uint32_t* tile_live, uint32_t M,
                                const mipsf_grid_meta* meta, int layout, void* stream) {
@@ -1644,10 +1755,11 @@ uint64_t hashgrid_bwd_scratch_floats(const mipsf_grid_meta* meta, uint32_t M, in
 uint64_t hashgrid_counter_words(const mipsf_grid_meta* meta) {
     GridLevels g;
     if (to_levels(meta, g)) return 0;
-    return make_plan(g, 1).w_items;              // {counts | head, tickets | first | parts}: independent of the batch size
+    return make_plan(g, 1).w_items;              // {counts | head, tickets | arrivals | first | parts}: independent of the batch size
 }
 }  // namespace mipsf
 extern "C" {
+
 
 #ifdef MIPSF_SC_TRACE
 // word offset of the trace rows, their capacity and the first bin of every level (diagnosis builds only)
@@ -1688,7 +1800,7 @@ static int check_plan(const ScatterPlan& plan, const GridLevels& g, uint32_t M) 
 static int launch_route(const float* x, const float* dout, int layout, uint32_t* ws, uint32_t* cw, bool clear, uint32_t M,
                         const GridLevels& g, const ScatterPlan& plan, hipStream_t s) {
     if (clear) {
-        const uint32_t nz = plan.w_nitems + 4;   // bin counts, queue head, tickets
+        const uint32_t nz = plan.w_first;        // bin counts, queue head, tickets, arrivals
         hipLaunchKernelGGL(scatter_zero_kernel, dim3((nz + 255) / 256), dim3(256), 0, s, cw, nz);
     }
     const uint32_t rb = route_groups(g.n_levels) * ((M + RT_BLOCK * SC_ROUTE_UNR - 1) / (RT_BLOCK * SC_ROUTE_UNR));
@@ -1724,6 +1836,10 @@ static int hashgrid_bwd_impl(const float* x, const float* params, const float* d
     hipStream_t s = (hipStream_t)stream;
     ScatterPlan plan = make_plan(g, M);
     plan.fresh = fresh ? 1u : 0u;
+    {   // experiments: the split bins folded by a launch of their own, as before the fold moved into the accumulate kernel
+        const char* e = getenv("MIPSF_SC_FOLD_LAUNCH");
+        plan.fold_launch = (e && e[0] && e[0] != '0') ? 1u : 0u;
+    }
     if (int rc = check_plan(plan, g, M)) return rc;
     uint32_t* ws = reinterpret_cast<uint32_t*>(scratch);
     uint32_t* cw = counters ? counters : ws;     // (without a kept block the counters sit at the front of the scratch)
@@ -1757,9 +1873,11 @@ static int hashgrid_bwd_impl(const float* x, const float* params, const float* d
         if (layout == MIPSF_FEAT_AOS) SCATTER(MIPSF_FEAT_AOS); else SCATTER(MIPSF_FEAT_LEVEL_MAJOR);
 #undef SCATTER
         if (int e = check_launch("hashgrid_scatter")) return e;
-        hipLaunchKernelGGL(hashgrid_scatter_reduce_kernel, dim3(plan.n_bins, (plan.max_slice + 255) / 256), dim3(256), 0, s,
-                           dparams, g, plan, ws, cw);
-        if (int e = check_launch("hashgrid_scatter_reduce")) return e;
+        if (plan.fold_launch) {
+            hipLaunchKernelGGL(hashgrid_scatter_reduce_kernel, dim3(plan.n_bins, (plan.max_slice + 255) / 256), dim3(256), 0, s,
+                               dparams, g, plan, ws, cw);
+            if (int e = check_launch("hashgrid_scatter_reduce")) return e;
+        }
     }
     if (dx) {
         uint32_t nchunk;

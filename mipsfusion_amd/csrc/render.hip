@@ -122,13 +122,16 @@ __global__ __launch_bounds__(RAYS_PER_BLOCK * MIPSF_WAVE) void sample_rays_kerne
 // Row gather of the ray table + ray construction from the pose parameters + sample placement in ONE launch (they were
 // gather_pose_rays_fwd_kernel + sample_rays_kernel, a 5 us launch each in every iteration; rays_o / rays_d never leave
 // the registers).  Same arithmetic and NaN conventions as the two kernels.  Wave per ray.
+// wants_dx (optional): one word per ray, 0 when the ray's pose is one of the F fixed ones -- the gradient of its points
+// reaches no parameter (place_pose_bwd_kernel drops the rows of the fixed poses) -- else 1; an owner out of range counts as
+// pose 0, as in the backward.
 MIPSF_SINGLE_FP32 __global__ __launch_bounds__(RAYS_PER_BLOCK * MIPSF_WAVE) void gather_pose_place_kernel(
     const float* __restrict__ db, uint64_t n_rows, const int64_t* __restrict__ idx, const float* __restrict__ fixed,
     const float* __restrict__ rot, const float* __restrict__ trans, int F, int K, const int64_t* __restrict__ owner,
     const float* __restrict__ noise, const float* __restrict__ z_uniform, const float* __restrict__ z_near_off,
     const float* __restrict__ z_near_nodepth, PlaceCfg pc, NormCfg nc, float* __restrict__ d_cam, float* __restrict__ rgb,
     float* __restrict__ depth, float* __restrict__ z_vals, float* __restrict__ xn, uint32_t* __restrict__ counts,
-    uint32_t N) {
+    uint32_t* __restrict__ wants_dx, uint32_t N) {
     __shared__ float zs[RAYS_PER_BLOCK][MAX_S];
     __shared__ float sb[RAYS_PER_BLOCK][MAX_S];
     __shared__ float sa[MAX_S];
@@ -152,6 +155,7 @@ MIPSF_SINGLE_FP32 __global__ __launch_bounds__(RAYS_PER_BLOCK * MIPSF_WAVE) void
     int64_t p = owner[n];
     if (p < 0) p += F + K;
     const bool in_range = p >= 0 && p < F + K;
+    if (wants_dx != nullptr && lane == 0) wants_dx[n] = (in_range ? (int)p : 0) >= F ? 1u : 0u;
     const Mat34 m = load_pose(fixed, rot, trans, F, in_range ? (int)p : 0);
     const float dx = in_range ? v[0] : __builtin_nanf(""), dy = v[1], dz = v[2];
     float o[3], dv[3];
@@ -816,11 +820,12 @@ int mipsf_sample_rays(const float* rays_o, const float* rays_d, const float* tar
     return check_launch("sample_rays");
 }
 
-int mipsf_gather_pose_place_fwd(const float* db, uint64_t n_rows, const int64_t* idx, const float* fixed_poses,
-                                const float* rot, const float* trans, uint32_t F, uint32_t K, const int64_t* owner,
-                                const float* noise, const float* z_uniform, const float* z_near_offsets,
-                                const float* z_near_nodepth, const mipsf_render_cfg* cfg, float* d_cam, float* rgb,
-                                float* depth, float* z_vals, float* xn, uint32_t* counts, uint32_t N, void* stream) {
+static int gather_pose_place_fwd(const float* db, uint64_t n_rows, const int64_t* idx, const float* fixed_poses,
+                                 const float* rot, const float* trans, uint32_t F, uint32_t K, const int64_t* owner,
+                                 const float* noise, const float* z_uniform, const float* z_near_offsets,
+                                 const float* z_near_nodepth, const mipsf_render_cfg* cfg, float* d_cam, float* rgb,
+                                 float* depth, float* z_vals, float* xn, uint32_t* counts, uint32_t* wants_dx, uint32_t N,
+                                 void* stream) {
     if (N == 0) return 0;
     MIPSF_REQUIRE(cfg && db && idx && owner && d_cam && rgb && depth && z_vals && xn, "null pointer");
     MIPSF_REQUIRE(z_uniform || cfg->n_uniform == 0, "null pointer: z_uniform with n_uniform = %u", cfg->n_uniform);
@@ -838,8 +843,27 @@ int mipsf_gather_pose_place_fwd(const float* db, uint64_t n_rows, const int64_t*
     hipLaunchKernelGGL(gather_pose_place_kernel, dim3((N + RAYS_PER_BLOCK - 1) / RAYS_PER_BLOCK),
                        dim3(RAYS_PER_BLOCK * MIPSF_WAVE), 0, (hipStream_t)stream, db, n_rows, idx, fixed_poses, rot, trans,
                        (int)F, (int)K, owner, noise, z_uniform, z_near_offsets, z_near_nodepth, pc, make_norm(*cfg), d_cam, rgb,
-                       depth, z_vals, xn, counts, N);
+                       depth, z_vals, xn, counts, wants_dx, N);
     return check_launch("gather_pose_place");
+}
+
+int mipsf_gather_pose_place_fwd(const float* db, uint64_t n_rows, const int64_t* idx, const float* fixed_poses,
+                                const float* rot, const float* trans, uint32_t F, uint32_t K, const int64_t* owner,
+                                const float* noise, const float* z_uniform, const float* z_near_offsets,
+                                const float* z_near_nodepth, const mipsf_render_cfg* cfg, float* d_cam, float* rgb,
+                                float* depth, float* z_vals, float* xn, uint32_t* counts, uint32_t N, void* stream) {
+    return gather_pose_place_fwd(db, n_rows, idx, fixed_poses, rot, trans, F, K, owner, noise, z_uniform, z_near_offsets,
+                                 z_near_nodepth, cfg, d_cam, rgb, depth, z_vals, xn, counts, nullptr, N, stream);
+}
+int mipsf_gather_pose_place_fwd_masked(const float* db, uint64_t n_rows, const int64_t* idx, const float* fixed_poses,
+                                       const float* rot, const float* trans, uint32_t F, uint32_t K, const int64_t* owner,
+                                       const float* noise, const float* z_uniform, const float* z_near_offsets,
+                                       const float* z_near_nodepth, const mipsf_render_cfg* cfg, float* d_cam, float* rgb,
+                                       float* depth, float* z_vals, float* xn, uint32_t* counts, uint32_t* wants_dx, uint32_t N,
+                                       void* stream) {
+    MIPSF_REQUIRE(wants_dx != nullptr || N == 0, "null wants_dx");
+    return gather_pose_place_fwd(db, n_rows, idx, fixed_poses, rot, trans, F, K, owner, noise, z_uniform, z_near_offsets,
+                                 z_near_nodepth, cfg, d_cam, rgb, depth, z_vals, xn, counts, wants_dx, N, stream);
 }
 
 }  // extern "C"

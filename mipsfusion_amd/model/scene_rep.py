@@ -72,10 +72,14 @@ class _QueryFn(torch.autograd.Function):
     partial backwards all behave as for any torch module).  ``JointEncoding.accumulate_param_grads_in_place = True``
     (opt-in, used by bench.py and the captured training loops) makes the backward add them straight into ``.grad``
     instead -- no 36 MB zero-fill + add pass per iteration -- which is only valid for plain ``loss.backward()``
-    accumulation loops; it is ignored for a parameter that is not a leaf or carries tensor hooks."""
+    accumulation loops; it is ignored for a parameter that is not a leaf or carries tensor hooks.
+
+    ray_mask (optional, int32 [N] for N rays of M / N consecutive samples): 0 = the gradient of this ray's points reaches no
+    parameter (``forward_from_table``: a ray of a fixed pose).  The grid's Jacobian of those samples is neither stored nor read
+    and their d x is returned as exact zeros; every other gradient is unchanged bit for bit."""
 
     @staticmethod
-    def forward(ctx, xn, owner, grid_params, *weights):
+    def forward(ctx, xn, owner, grid_params, ray_mask, *weights):
         xn = ops._f32c(xn)
         M = xn.shape[0]
         meta = owner.embed_fn.meta
@@ -89,7 +93,7 @@ class _QueryFn(torch.autograd.Function):
         if ctx.needs_input_grad[2] and owner.route_ahead and M >= _ROUTE_AHEAD_MIN_M and not ops.resolve_deterministic(owner.deterministic):
             routed = ops.hashgrid_route_ahead(xn, meta)
         if ctx.needs_input_grad[0]:
-            feat, jac = ops.hashgrid_fwd(xn, grid_params.detach(), meta, FEAT_LEVEL_MAJOR, with_jac=True)
+            feat, jac = ops.hashgrid_fwd(xn, grid_params.detach(), meta, FEAT_LEVEL_MAJOR, with_jac=True, ray_mask=ray_mask)
         else:
             feat = ops.hashgrid_fwd(xn, grid_params.detach(), meta, FEAT_LEVEL_MAJOR)
         need = any(ctx.needs_input_grad)
@@ -113,7 +117,7 @@ class _QueryFn(torch.autograd.Function):
         lean = bool(need and prec in ops.SPLIT_PRECISIONS and owner.wgrad_precision in ("auto", "stream_" + prec) and owner.lean_record)
         # a frozen decoder (tracking: only the points need a gradient): the chain reads the ReLU masks and nothing else of the
         # record -- the 1 KB of activations per sample would be written for nobody
-        masks_only = bool(need and prec in ops.SPLIT_PRECISIONS and not any(ctx.needs_input_grad[3:]))
+        masks_only = bool(need and prec in ops.SPLIT_PRECISIONS and not any(ctx.needs_input_grad[4:]))
         out, saved = ops.decoder_fwd(packed, feat, FEAT_LEVEL_MAJOR, xn, None, M,
                                      save="masks" if masks_only else ("lean" if lean else need), precision=prec, packed16=packed16)
         ctx.lean = lean and not masks_only
@@ -125,6 +129,7 @@ class _QueryFn(torch.autograd.Function):
             torch.cuda.current_stream(xn.device).wait_event(routed[1])
         ctx.routed = routed
         ctx.owner, ctx.M, ctx.meta, ctx.has_jac = owner, M, meta, jac is not None
+        ctx.ray_mask = ray_mask if jac is not None else None      # (an int32 input: no gradient, kept as an attribute)
         ctx.save_for_backward(xn, feat, out, saved, packed, grid_params, *weights, *([jac] if jac is not None else []))
         return out
 
@@ -132,7 +137,7 @@ class _QueryFn(torch.autograd.Function):
     def backward(ctx, dout):
         xn, feat, out, saved, packed, grid_params, *weights = ctx.saved_tensors
         jac = weights.pop() if ctx.has_jac else None
-        need_w = any(ctx.needs_input_grad[3:])
+        need_w = any(ctx.needs_input_grad[4:])
         need_g = ctx.needs_input_grad[2]
         need_x = ctx.needs_input_grad[0]
         if ctx.tile_live is not None:
@@ -144,7 +149,7 @@ class _QueryFn(torch.autograd.Function):
         grads = None
         if need_w:
             grads = []
-            for w, need in zip(weights, ctx.needs_input_grad[3:]):
+            for w, need in zip(weights, ctx.needs_input_grad[4:]):
                 if direct and need:
                     if w.grad is None:
                         w.grad = torch.zeros_like(w)
@@ -171,11 +176,12 @@ class _QueryFn(torch.autograd.Function):
                              dparams_zero=(not direct) or fresh_grad or ctx.owner.grid_grad_is_zero_at_backward, deterministic=det)
             ctx.routed = None
         if need_x:
-            ops.hashgrid_dx_from_jac(jac, dfeat, dx, ctx.meta, FEAT_LEVEL_MAJOR, tiles=tiles)   # (dfeat is untouched since the chain wrote it)
+            ops.hashgrid_dx_from_jac(jac, dfeat, dx, ctx.meta, FEAT_LEVEL_MAJOR, tiles=tiles,   # (dfeat is untouched since the chain wrote it)
+                                     ray_mask=ctx.ray_mask)
         w_out = [None] * len(weights)
         if need_w and not direct:
-            w_out = [g if need else None for g, need in zip(grads, ctx.needs_input_grad[3:])]
-        return (dx if need_x else None, None, None if direct else dparams, *w_out)
+            w_out = [g if need else None for g, need in zip(grads, ctx.needs_input_grad[4:])]
+        return (dx if need_x else None, None, None if direct else dparams, None, *w_out)
 
 
 class _RenderFn(torch.autograd.Function):
@@ -278,6 +284,9 @@ class JointEncoding(nn.Module):
         # beside the persistent decoder forward, take 211 us instead of 70 and slow that kernel from 99 to 137 us -- the
         # step gets 40 us LONGER (0.88 -> 0.92 ms).  It pays only where the forward leaves CUs idle.
         self.route_ahead = False
+        # forward_from_table: the rays of the fixed poses keep no grid Jacobian and get no d x (exact: the pose backward drops
+        # their rows).  False (experiments, MIPSF_NO_DX_MASK=1): every ray keeps both, as before the mask
+        self.mask_fixed_rays = os.environ.get("MIPSF_NO_DX_MASK", "0") != "1"
         # ray-data-parallel training (mipsfusion_amd/ray_dp.py sets it): the rays handed to forward() are ONE SHARE of the
         # iteration's batch; the callable sums a small fp64 vector over the ranks, the losses (and their gradients) are then
         # those of the WHOLE batch -- fs_weight / sdf_weight from the batch's counts (helper_functions/utils.py:43-47), the
@@ -335,13 +344,13 @@ class JointEncoding(nn.Module):
                 self._tables[key] = (zu.contiguous(), None, None)
         return self._tables[key]
 
-    def _query(self, x32):
+    def _query(self, x32, ray_mask=None):
         # the 16-bit decoder kernels address a call's samples through 4 GB buffer resources: at most 2^24 - 1 samples per
         # launch.  Forward-only consumers (a 256^3 mesher grid in one call, Mesher.py:342-630) are cut into launches of 2^23
         M = x32.shape[0]
         if M >= _MAX_QUERY and not (torch.is_grad_enabled() and (x32.requires_grad or any(p.requires_grad for p in self.parameters()))):
             return torch.cat([self._query(x32[i:i + _QUERY_CHUNK]) for i in range(0, M, _QUERY_CHUNK)], 0)
-        return _QueryFn.apply(x32, self, self.embed_fn.params, *self.decoder.ordered_parameters())
+        return _QueryFn.apply(x32, self, self.embed_fn.params, ray_mask, *self.decoder.ordered_parameters())
 
     def __getstate__(self):
         d = self.__dict__.copy()        # (pinned staging buffers and their events stay with this process)
@@ -365,6 +374,7 @@ class JointEncoding(nn.Module):
         new.wgrad_precision = self.wgrad_precision
         new.lean_record = self.lean_record
         new.route_ahead = self.route_ahead
+        new.mask_fixed_rays = self.mask_fixed_rays
         new.deterministic = self.deterministic
         new._frozen_pack = None
         new.train(self.training)
@@ -512,10 +522,11 @@ class JointEncoding(nn.Module):
         if rc.perturb and noise is None:
             raise ValueError("forward_from_table needs the jitter noise as a device tensor")
         tables = self._linspace_tables(table.device, True)
-        trgb, td, z_vals, xn, counts = ops.GatherPosePlaceFn.apply(rot, trans, fixed_poses, owner, table, rows,
-                                                                   ops._f32c(noise) if rc.perturb else None, tables, rc, S,
-                                                                   accumulate_in_place)
-        raw = self._query(xn)
+        trgb, td, z_vals, xn, counts, wants_dx = ops.GatherPosePlaceFn.apply(rot, trans, fixed_poses, owner, table, rows,
+                                                                             ops._f32c(noise) if rc.perturb else None, tables,
+                                                                             rc, S, accumulate_in_place)
+        # (the rays of the fixed poses: nobody uses the gradient of their points -- no Jacobian, no d x for them)
+        raw = self._query(xn, wants_dx if self.mask_fixed_rays else None)
         res = _RenderFn.apply(raw, z_vals, trgb, td, counts, rc, N, S, True, self._objective_weights(raw.device),
                               self.ray_share_reduce)
         rgb, depth, losses = res[0], res[1], res[5]

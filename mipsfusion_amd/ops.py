@@ -58,17 +58,26 @@ def _f32c(t: torch.Tensor) -> torch.Tensor:
 
 
 # ------------------------------------------------------------------------------ hash grid
-def hashgrid_fwd(x: torch.Tensor, params: torch.Tensor, meta, layout=FEAT_AOS, with_jac: bool = False):
-    """with_jac: also return d out / d x ([L, 3, M, 2]) for `hashgrid_dx_from_jac` (use when x needs a gradient)."""
+def hashgrid_fwd(x: torch.Tensor, params: torch.Tensor, meta, layout=FEAT_AOS, with_jac: bool = False, ray_mask=None):
+    """with_jac: also return d out / d x ([L, 3, M, 2]) for `hashgrid_dx_from_jac` (use when x needs a gradient).
+    ray_mask (with_jac only): int32 [N], x = N rays of M / N consecutive samples; the Jacobian of the samples of a ray with
+    a zero word is not stored (nobody uses d x of that ray) -- hand the same mask to `hashgrid_dx_from_jac`."""
     M = x.shape[0]
     nf = meta.n_levels * meta.n_features
     out = torch.empty((M, nf) if layout == FEAT_AOS else (meta.n_levels, M, meta.n_features),
                       dtype=torch.float32, device=x.device)
     if with_jac:
         jac = torch.empty((meta.n_levels, 3, M, 2), dtype=torch.float32, device=x.device)
+        if ray_mask is not None and (ray_mask.shape[0] == 0 or M % ray_mask.shape[0] != 0):
+            raise RuntimeError(f"ray mask: {M} samples are not whole rays of {ray_mask.shape[0]} rays")
         with _timed("hashgrid_fwd"):
-            check(lib().mipsf_hashgrid_fwd(dptr(x), dptr(params), dptr(out), dptr(jac), M, C.byref(meta), layout,
-                                           stream_ptr()), "hashgrid_fwd (with the Jacobian)")
+            if ray_mask is not None:
+                check(lib().mipsf_hashgrid_fwd_masked(dptr(x), dptr(params), dptr(out), dptr(jac), dptr(ray_mask, torch.int32),
+                                                      M // ray_mask.shape[0], M, C.byref(meta), layout, stream_ptr()),
+                      "hashgrid_fwd (with the Jacobian, masked)")
+            else:
+                check(lib().mipsf_hashgrid_fwd(dptr(x), dptr(params), dptr(out), dptr(jac), M, C.byref(meta), layout,
+                                               stream_ptr()), "hashgrid_fwd (with the Jacobian)")
         return out, jac
     with _timed("hashgrid_fwd"):
         check(lib().mipsf_hashgrid_fwd(dptr(x), dptr(params), dptr(out), None, M, C.byref(meta), layout, stream_ptr()),
@@ -85,12 +94,25 @@ class LiveList:
         self.buf = buf
 
 
-def hashgrid_dx_from_jac(jac, dout, dx, meta, layout=FEAT_AOS, tiles=None):
+def hashgrid_dx_from_jac(jac, dout, dx, meta, layout=FEAT_AOS, tiles=None, ray_mask=None):
     """dx += J . dout with the Jacobian saved by hashgrid_fwd(with_jac=True).  tiles: the live-tile lists (or the LiveList) that
     ``decoder_bwd(..., return_tiles=True)`` hands back together with THIS `dout` -- the samples of the other tiles have a
     zero gradient and are left out (their Jacobian is not read).  Only pass lists that describe `dout` as it is now: a
-    gradient added into `dout` afterwards (a feature regulariser, say) makes them stale -- leave `tiles` out then."""
+    gradient added into `dout` afterwards (a feature regulariser, say) makes them stale -- leave `tiles` out then.
+    ray_mask: the mask `hashgrid_fwd` was given; the visited samples of a masked ray get dx = +0 (what the decoder's backward
+    left there is dropped: nobody uses it) and their Jacobian -- never written -- is not read."""
     M = dx.shape[0]
+    if ray_mask is not None:
+        if ray_mask.shape[0] == 0 or M % ray_mask.shape[0] != 0:
+            raise RuntimeError(f"ray mask: {M} samples are not whole rays of {ray_mask.shape[0]} rays")
+        lst = isinstance(tiles, LiveList)
+        with _timed("hashgrid_dx"):
+            check(lib().mipsf_hashgrid_dx_from_jac_masked(dptr(jac), dptr(dout), dptr(dx),
+                                                          None if lst else dptr(tiles, torch.int32),
+                                                          dptr(tiles.buf, torch.int32) if lst else None,
+                                                          dptr(ray_mask, torch.int32), M // ray_mask.shape[0], M,
+                                                          C.byref(meta), layout, stream_ptr()), "hashgrid_dx_from_jac_masked")
+        return
     if isinstance(tiles, LiveList):
         with _timed("hashgrid_dx"):
             check(lib().mipsf_hashgrid_dx_from_jac_list(dptr(jac), dptr(dout), dptr(dx), dptr(tiles.buf, torch.int32), M,
@@ -840,7 +862,8 @@ def gather_pose_rays(table, rows, rot, trans, fixed_poses, owner, accumulate_in_
 class GatherPosePlaceFn(torch.autograd.Function):
     """Row gather of the ray table + rays from the pose Parameters + sample placement (``gather_pose_rays`` followed by
     ``JointEncoding``'s placement: keyframeSet.py:264-290, mipsfusion.py:320-322, scene_rep.py:156-179) as ONE launch
-    each way: -> (rgb [N,3], depth [N,1], z_vals [N,S], xn [N*S,3], counts [N,2]); the gradient of xn reaches rot / trans."""
+    each way: -> (rgb [N,3], depth [N,1], z_vals [N,S], xn [N*S,3], counts [N,2], wants_dx [N] int32); the gradient of xn
+    reaches rot / trans.  wants_dx: 0 for the rays of the fixed poses, whose d xn the backward drops."""
 
     @staticmethod
     def forward(ctx, rot, trans, fixed, owner, table, rows, noise, tables, rc, S, in_place):
@@ -855,21 +878,23 @@ class GatherPosePlaceFn(torch.autograd.Function):
         e = lambda *sh: torch.empty(sh, dtype=torch.float32, device=dev)       # noqa: E731
         d_cam, rgb, depth, z_vals, xn = e(N, 3), e(N, 3), e(N, 1), e(N, S), e(N * S, 3)
         counts = torch.empty((N, 2), dtype=torch.int32, device=dev)
+        wants_dx = torch.empty((N,), dtype=torch.int32, device=dev)
         zu, zoff, znd = tables
         with _timed("sample_rays"):
-            check(lib().mipsf_gather_pose_place_fwd(dptr(flat), flat.shape[0], dptr(rows, torch.int64), dptr(fixed), dptr(rot),
-                                                    dptr(trans), F, K, dptr(owner, torch.int64), dptr(noise), dptr(zu),
-                                                    dptr(zoff), dptr(znd), C.byref(rc), dptr(d_cam), dptr(rgb), dptr(depth),
-                                                    dptr(z_vals), dptr(xn), dptr(counts, torch.int32), N, stream_ptr()),
+            check(lib().mipsf_gather_pose_place_fwd_masked(dptr(flat), flat.shape[0], dptr(rows, torch.int64), dptr(fixed),
+                                                           dptr(rot), dptr(trans), F, K, dptr(owner, torch.int64), dptr(noise),
+                                                           dptr(zu), dptr(zoff), dptr(znd), C.byref(rc), dptr(d_cam), dptr(rgb),
+                                                           dptr(depth), dptr(z_vals), dptr(xn), dptr(counts, torch.int32),
+                                                           dptr(wants_dx, torch.int32), N, stream_ptr()),
                   "gather_pose_place_fwd")
         ctx.F, ctx.K, ctx.N, ctx.S, ctx.rc = F, K, N, S, rc
         ctx.save_for_backward(rot, owner, d_cam, z_vals)
-        ctx.mark_non_differentiable(rgb, depth, z_vals, counts)
+        ctx.mark_non_differentiable(rgb, depth, z_vals, counts, wants_dx)
         ctx.set_materialize_grads(False)
-        return rgb, depth, z_vals, xn, counts
+        return rgb, depth, z_vals, xn, counts, wants_dx
 
     @staticmethod
-    def backward(ctx, _g_rgb, _g_depth, _g_z, dxn, _g_counts):
+    def backward(ctx, _g_rgb, _g_depth, _g_z, dxn, _g_counts, _g_wants):
         if dxn is None:
             return (None,) * 11
         rot, owner, d_cam, z_vals = ctx.saved_tensors
