@@ -15,7 +15,8 @@ _POSE_GRAPH = ("adjacent_pairs", "global_ba_gate", "build_edges", "pose_graph_en
 _SUBMAP_MANAGER = ("SubmapManager", "Decision", "derive_schedule", "frame_stats_enqueue", "overlap_enqueue")
 _EVALUATE = ("sample_surface", "nearest_distance", "distance_stats", "reconstruction_metrics", "cull_to_views", "ReconMetrics",
              "DistanceStats")
-_MESH_RENDER = ("render_mesh_depth", "depth_l1", "visible_points", "DepthMetrics")
+_MESH_RENDER = ("render_mesh_depth", "depth_l1", "visible_points", "DepthMetrics", "render_mesh", "vertex_normals", "mesh_render_metrics",
+                "MeshRender", "MeshRenderMetrics")
 _TSDF = ("TSDFVolume", "TSDFCounts", "tsdf_mesh_from_frames", "mesh_from_rendered_depth", "Raycast", "TrackResult", "tsdf_odometry")
 # (the function image_metrics.image_metrics is reached through its module: the package attribute of that name IS the module)
 _IMAGE_METRICS = ("psnr", "ssim", "ms_ssim", "render_metrics", "gaussian_window", "ImageMetrics", "RenderMetrics")
@@ -42,7 +43,7 @@ def __getattr__(name):
     if name in _EVALUATE:                   # scoring a mesh against ground truth (mipsfusion_amd/evaluate.py), the same way
         from . import evaluate
         return getattr(evaluate, name)
-    if name in _MESH_RENDER:                # a mesh as depth images, depth L1, occlusion (mipsfusion_amd/mesh_render.py), the same way
+    if name in _MESH_RENDER:                # a mesh as depth, colour and normal images, depth L1, occlusion (mipsfusion_amd/mesh_render.py)
         from . import mesh_render
         return getattr(mesh_render, name)
     if name in _TSDF:                       # depth frames fused into a TSDF volume and meshed (mipsfusion_amd/tsdf.py), the same way

@@ -429,6 +429,26 @@ IMAGE_SIGNATURES = {
 }
 
 
+# include/mipsf_shade.h (per-vertex normals; the face image of mipsf_raster_depth as colour, normal and head-lit images)
+SHADE_TILE, SHADE_MAX_FACES, SHADE_MAX_VERTICES, SHADE_MAX_SIDE, SHADE_MAX_PIXELS, SHADE_MAX_ITEMS = 8, 1 << 30, 0x7FFFFFFF, 8192, 1 << 30, 0x7FFFFFFF
+SHADE_SHORT_SEGMENT = 32
+SHADE_WS_VERTEX_NORMALS = 1
+SHADE_FLAT, SHADE_SMOOTH = 1, 2
+SHADE_RECORD_WORDS = 2                     # uint64 hits, shaded
+ShadeVertexNormalsArgs = _args("ShadeVertexNormalsArgs", [("V", _CU), ("F", _CU), ("reserved", _CU), ("vertices", _VP), ("faces", _VP),
+                                                          ("normals", _VP), ("workspace", _VP)])
+ShadePixelsArgs = _args("ShadePixelsArgs", [("V", _CU), ("F", _CU), ("n", _CU), ("H", _CU), ("W", _CU), ("flags", _CU), ("reserved", _CU),
+                                            ("fx", C.c_double), ("fy", C.c_double), ("cx", C.c_double), ("cy", C.c_double),
+                                            ("background", C.c_float * 3), ("reserved2", C.c_float), ("vertices", _VP), ("faces", _VP),
+                                            ("poses", _VP), ("face", _VP), ("colors", _VP), ("vertex_normals", _VP), ("color", _VP),
+                                            ("normals", _VP), ("shaded", _VP), ("record", _VP)])
+SHADE_SIGNATURES = {
+    "mipsf_shade_workspace_bytes": (_U64, [_I, _U32, _U32]),
+    "mipsf_shade_vertex_normals": (_I, [C.POINTER(ShadeVertexNormalsArgs), _P]),
+    "mipsf_shade_pixels": (_I, [C.POINTER(ShadePixelsArgs), _P]),
+}
+
+
 def buffer_size(which: int, n: int = 0, a: int = 0, b: int = 0, meta=None) -> int:
     """mipsf_buffer_size: elements of a scratch / record buffer (SIZE_* above)."""
     v = lib().mipsf_buffer_size(which, n, a, b, C.byref(meta) if meta is not None else None)
@@ -464,7 +484,8 @@ def lib() -> C.CDLL:
                                        + list(COMPACT_SIGNATURES.items()) + list(POSEGRAPH_SIGNATURES.items())
                                        + list(SUBMAP_SIGNATURES.items()) + list(EVAL_SIGNATURES.items())
                                        + list(RASTER_SIGNATURES.items()) + list(TSDF_SIGNATURES.items())
-                                       + list(IMAGE_SIGNATURES.items()) + list(TRACK_SIGNATURES.items())):
+                                       + list(IMAGE_SIGNATURES.items()) + list(TRACK_SIGNATURES.items())
+                                       + list(SHADE_SIGNATURES.items())):
             fn = getattr(handle, name)
             fn.restype = res
             fn.argtypes = args
