@@ -397,6 +397,19 @@ TRACK_SIGNATURES = {
     "mipsf_track_raycast": (_I, [C.POINTER(TrackRaycastArgs), _P]),
     "mipsf_track_register": (_I, [C.POINTER(TrackRegisterArgs), _P]),
 }
+# include/mipsf_track_color.h (the same registration with a photometric row per pair against the ray cast's colour image)
+TRACK_COLOR_RESULT_DOUBLES, TRACK_WS_REGISTER_COLOR = 22, 3
+TrackRegisterColorArgs = _args("TrackRegisterColorArgs", [("H", _CU), ("W", _CU), ("max_iteration", _CU),
+                                                          ("fx", C.c_double), ("fy", C.c_double), ("cx", C.c_double), ("cy", C.c_double),
+                                                          ("depth_max", C.c_double), ("max_dist", C.c_double), ("relative_fitness", C.c_double),
+                                                          ("relative_rmse", C.c_double), ("color_weight", C.c_double),
+                                                          ("max_color_diff", C.c_double), ("relative_color_rmse", C.c_double),
+                                                          ("model_depth", _VP), ("model_normals", _VP), ("model_color", _VP), ("pose_ref", _VP),
+                                                          ("live", _VP), ("live_color", _VP), ("pose_init", _VP), ("result", _VP),
+                                                          ("pose_out", _VP), ("partner", _VP), ("color_partner", _VP), ("workspace", _VP)])
+TRACK_COLOR_SIGNATURES = {
+    "mipsf_track_register_color": (_I, [C.POINTER(TrackRegisterColorArgs), _P]),
+}
 
 
 # include/mipsf_image.h (two image stacks compared: error sums, valid-region SSIM and its cs term, the MS-SSIM pyramid's 2 x 2 mean)
@@ -484,7 +497,7 @@ def lib() -> C.CDLL:
                                        + list(COMPACT_SIGNATURES.items()) + list(POSEGRAPH_SIGNATURES.items())
                                        + list(SUBMAP_SIGNATURES.items()) + list(EVAL_SIGNATURES.items())
                                        + list(RASTER_SIGNATURES.items()) + list(TSDF_SIGNATURES.items())
-                                       + list(IMAGE_SIGNATURES.items()) + list(TRACK_SIGNATURES.items())
+                                       + list(IMAGE_SIGNATURES.items()) + list(TRACK_SIGNATURES.items()) + list(TRACK_COLOR_SIGNATURES.items())
                                        + list(SHADE_SIGNATURES.items())):
             fn = getattr(handle, name)
             fn.restype = res

@@ -1,6 +1,7 @@
-// The finish step of a point-to-plane registration, stated once for its two users: icp.hip (nearest-neighbour pairs between two
-// clouds, include/mipsf_icp.h) and tsdf_track.hip (projective pairs between a depth frame and a ray-cast model,
-// include/mipsf_track.h).  Both leave the sums of the normal equations per block in partial[block][NSUM_PAD] and enqueue
+// The finish step of a point-to-plane registration, stated once for its users: icp.hip (nearest-neighbour pairs between two
+// clouds, include/mipsf_icp.h), tsdf_track.hip (projective pairs between a depth frame and a ray-cast model,
+// include/mipsf_track.h) and track_color.hip (the same pairs with photometric rows added to the same sums,
+// include/mipsf_track_color.h).  All leave the sums of the normal equations per block in partial[block][NSUM_PAD] and enqueue
 // max_iteration + 1 evaluations; the `done` word makes the later ones return at once.  Device code only.
 #pragma once
 #include "common.h"
@@ -15,6 +16,7 @@ struct IcpState {
     double U[12];       // the update the next evaluation applies to its points, 3x4
     double prev_fitness, prev_rmse;
     uint32_t done, iter;
+    double prev_color_rmse;   // track_color.hip alone: the photometric rmse of the evaluation before
 };
 static_assert(sizeof(IcpState) <= 256, "IcpState");
 
@@ -33,11 +35,14 @@ __device__ __forceinline__ void icp_pair_sums(double c[NSUM], double px, double 
 }
 
 // One wave, st->done not set: add the partials in index order, judge the evaluation, and -- unless it was the last -- solve for
-// the next update.  COLS = NSUM: the fitness is over n_source; COLS = NSUM + 1: over the sum of column NSUM.  Every lane calls.
+// the next update.  COLS = NSUM: the fitness is over n_source; COLS = NSUM + 1: over the sum of column NSUM.  COLS = NSUM_PAD
+// (track_color.hip): as NSUM + 1, and column 30 counts photometric rows and column 31 sums their squared residuals; their rmse goes
+// to result[20..21] and the relative stop also needs it to have moved by less than rel_color.  Every lane calls.
 template <int COLS>
 __device__ __forceinline__ void icp_finish(const double* __restrict__ partial, uint32_t nb, uint32_t n_source, IcpState* st, uint32_t max_iteration,
-                                           double rel_fitness, double rel_rmse, double* __restrict__ result) {
-    static_assert(COLS == NSUM || COLS == NSUM + 1, "columns of the partials");
+                                           double rel_fitness, double rel_rmse, double* __restrict__ result, double rel_color = 0.0) {
+    static_assert(COLS == NSUM || COLS == NSUM + 1 || COLS == NSUM_PAD, "columns of the partials");
+    constexpr bool COLOR = COLS == NSUM_PAD;
     __shared__ double S[NSUM_PAD];
     __shared__ double A[6][6];
     __shared__ double x[6];
@@ -53,10 +58,15 @@ __device__ __forceinline__ void icp_finish(const double* __restrict__ partial, u
     const double fitness = sources > 0.0 ? pairs / sources : 0.0;
     const double rmse = pairs > 0.0 ? sqrt(S[28] / pairs) : 0.0;
     const uint32_t iter = st->iter;
+    double color_rmse = 0.0;
+    if constexpr (COLOR) color_rmse = S[30] > 0.0 ? sqrt(S[31] / S[30]) : 0.0;
     bool stop = iter >= max_iteration;
-    if (iter > 0 && fabs(st->prev_fitness - fitness) < rel_fitness && fabs(st->prev_rmse - rmse) < rel_rmse) stop = true;
+    bool still = iter > 0 && fabs(st->prev_fitness - fitness) < rel_fitness && fabs(st->prev_rmse - rmse) < rel_rmse;
+    if constexpr (COLOR) still = still && fabs(st->prev_color_rmse - color_rmse) < rel_color;
+    if (still) stop = true;
     for (int j = 0; j < 16; ++j) result[j] = st->T[j];
     result[16] = pairs, result[17] = fitness, result[18] = rmse, result[19] = (double)iter;
+    if constexpr (COLOR) result[20] = S[30], result[21] = color_rmse;
     if (stop) {
         st->done = 1u;
         return;
@@ -112,6 +122,7 @@ __device__ __forceinline__ void icp_finish(const double* __restrict__ partial, u
         }
     for (int j = 0; j < 12; ++j) st->T[j] = Tn[j], st->U[j] = U[j];
     st->prev_fitness = fitness, st->prev_rmse = rmse;
+    if constexpr (COLOR) st->prev_color_rmse = color_rmse;
     st->iter = iter + 1u;
 }
 

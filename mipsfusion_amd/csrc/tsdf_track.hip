@@ -12,9 +12,11 @@
 #include "block_dev.h"
 #include "icp_dev.h"
 #include "tsdf_dev.h"
-#include "../../include/mipsf_track.h"
+#include "../../include/mipsf_track_color.h"
 
 namespace mipsf {
+uint64_t track_color_workspace_bytes(uint32_t H, uint32_t W);         // track_color.hip
+
 namespace {
 
 constexpr int TPB = 256;
@@ -333,6 +335,8 @@ extern "C" uint64_t mipsf_track_workspace_bytes(int which, uint32_t a, uint32_t 
         case MIPSF_TRACK_WS_REGISTER:
             if (a == 0 || b == 0 || a > MIPSF_TSDF_MAX_SIDE || b > MIPSF_TSDF_MAX_SIDE) return 0;
             return REG_STATE_BYTES + (uint64_t)blocks_for((uint64_t)a * b, TPB) * NSUM_PAD * sizeof(double);
+        case MIPSF_TRACK_WS_REGISTER_COLOR:
+            return track_color_workspace_bytes(a, b);
         default:
             return 0;
     }

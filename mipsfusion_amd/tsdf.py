@@ -7,6 +7,8 @@ DESIGN.md 4.19):
     TSDFVolume                 the state (tsdf, weight, optionally colour, all on the device) and integrate / volume / extract_mesh,
                                raycast (the volume as depth, normal and colour images) and track (a depth frame registered
                                against such images); kernels of ``csrc/tsdf_track.hip``, C ABI include/mipsf_track.h, DESIGN.md 4.21
+                               track(rgb=...) adds a photometric row per pair against the ray cast's colour, which holds the pose
+                               along walls: ``csrc/track_color.hip``, include/mipsf_track_color.h, DESIGN.md 4.23
     tsdf_odometry              depth frames -> poses: every frame registered against the ray cast of the volume, then fused
     tsdf_mesh_from_frames      depth frames + poses -> mesh.Mesh
     mesh_from_rendered_depth   model + poses -> rendered depth -> mesh.Mesh
@@ -48,6 +50,22 @@ class TrackResult(NamedTuple):
     fitness: float                   # pairs over the usable live pixels
     inlier_rmse: float
     iterations: int
+
+
+class ColorTrackResult(NamedTuple):
+    pose: torch.Tensor               # the fields of TrackResult, then the photometric side of the last evaluation
+    transformation: torch.Tensor
+    n_correspondences: int
+    fitness: float
+    inlier_rmse: float
+    iterations: int
+    n_color: int                     # pairs that also gave a photometric row
+    color_rmse: float                # of the intensity residuals, intensities in the units of rgb
+
+
+# the colour term's weight against the geometric one (intensity^2 against metres^2): of 0.01, 0.1, 1 and 10 the one with the
+# smallest worst final error over a lone wall, two walls and a corner of the box room
+DEFAULT_COLOR_WEIGHT = 10.0
 
 
 def _device(device=None) -> torch.device:
@@ -183,21 +201,52 @@ class TSDFVolume:
     def track_enqueue(self, depth: torch.Tensor, K, pose_init: torch.Tensor, pose_ref: Optional[torch.Tensor] = None,
                       model: Optional[Raycast] = None, max_dist: Optional[float] = None, max_iteration: int = 30,
                       relative_fitness: float = 1e-6, relative_rmse: float = 1e-6, depth_max: float = math.inf, partner: bool = False,
-                      **raycast_kw):
+                      rgb: Optional[torch.Tensor] = None, color_weight: Optional[float] = None, max_color_diff: float = math.inf,
+                      relative_color_rmse: float = 1e-6, **raycast_kw):
         """The ray cast from pose_ref (unless ``model`` is given) and mipsf_track_register; nothing is read back.  depth fp32 [H,W],
         pose_init and pose_ref fp32 [4,4], all on the device -> (result float64 [20]: T row major, correspondences, fitness, inlier
-        rmse, iterations; pose fp32 [4,4]) on the device (, partner int32 [H,W])"""
-        _lib.dptr(depth), _lib.dptr(pose_init), _lib.dptr(pose_ref)
+        rmse, iterations; pose fp32 [4,4]) on the device (, partner int32 [H,W]).
+        With ``rgb`` fp32 [H,W,3] on the device the ray cast also gives the model's colour and mipsf_track_register_color registers
+        depth and colour (``color_weight``: DEFAULT_COLOR_WEIGHT unless given) -> (result float64 [22]: the same, then photometric
+        rows and their rmse; pose) (, partner, color_partner int32 [H,W]: 1 where the pixel gave a photometric row)"""
+        _lib.dptr(depth), _lib.dptr(pose_init), _lib.dptr(pose_ref), _lib.dptr(rgb)
         pose_ref = pose_init if pose_ref is None else pose_ref
         if depth.dim() != 2 or tuple(pose_init.shape) != (4, 4) or tuple(pose_ref.shape) != (4, 4):
             raise ValueError(f"expected depth [H,W] and poses [4,4], got {tuple(depth.shape)}, {tuple(pose_init.shape)}, {tuple(pose_ref.shape)}")
         H, W = depth.shape
         fx, fy, cx, cy = (float(x) for x in _intrinsics(K))
+        if rgb is not None:
+            if self.color is None:
+                raise ValueError("rgb: the volume was made without colour (color=True)")
+            if tuple(rgb.shape) != (H, W, 3):
+                raise ValueError(f"rgb: expected {(H, W, 3)}, got {tuple(rgb.shape)}")
+            if model is not None and model.color is None:
+                raise ValueError("model: tracking with rgb needs a ray cast made with color=True")
+            raycast_kw = dict(raycast_kw, color=True)
         if model is None:
             model = self.raycast_enqueue(pose_ref[None], K, H, W, **raycast_kw)
         if model.normals is None or tuple(model.depth.shape[-2:]) != (H, W) or model.depth.numel() != H * W:
             raise ValueError("model: one ray-cast view with normals, of the live frame's size")
         lib = _lib.lib()
+        if rgb is not None:
+            with torch.cuda.device(self.device):
+                ws = torch.empty(int(lib.mipsf_track_workspace_bytes(_lib.TRACK_WS_REGISTER_COLOR, H, W, 0)), dtype=torch.uint8, device=self.device)
+                result = torch.empty(_lib.TRACK_COLOR_RESULT_DOUBLES, dtype=torch.float64, device=self.device)
+                pose = torch.empty(4, 4, dtype=torch.float32, device=self.device)
+                mates = torch.empty(H, W, dtype=torch.int32, device=self.device) if partner else None
+                rows = torch.empty(H, W, dtype=torch.int32, device=self.device) if partner else None
+                a = _lib.TrackRegisterColorArgs.new(H=H, W=W, max_iteration=int(max_iteration), fx=fx, fy=fy, cx=cx, cy=cy, depth_max=float(depth_max),
+                                                    max_dist=self.trunc if max_dist is None else float(max_dist),
+                                                    relative_fitness=float(relative_fitness), relative_rmse=float(relative_rmse),
+                                                    color_weight=DEFAULT_COLOR_WEIGHT if color_weight is None else float(color_weight),
+                                                    max_color_diff=float(max_color_diff), relative_color_rmse=float(relative_color_rmse),
+                                                    model_depth=_lib.dptr(model.depth), model_normals=_lib.dptr(model.normals),
+                                                    model_color=_lib.dptr(model.color), pose_ref=pose_ref.data_ptr(), live=depth.data_ptr(),
+                                                    live_color=rgb.data_ptr(), pose_init=pose_init.data_ptr(), result=result.data_ptr(),
+                                                    pose_out=pose.data_ptr(), partner=_lib.dptr(mates, torch.int32),
+                                                    color_partner=_lib.dptr(rows, torch.int32), workspace=ws.data_ptr())
+                _lib.check(lib.mipsf_track_register_color(C.byref(a), _lib.stream_ptr()), "track_register_color")
+            return (result, pose, mates, rows) if partner else (result, pose)
         with torch.cuda.device(self.device):
             ws = torch.empty(int(lib.mipsf_track_workspace_bytes(_lib.TRACK_WS_REGISTER, H, W, 0)), dtype=torch.uint8, device=self.device)
             result = torch.empty(_lib.TRACK_RESULT_DOUBLES, dtype=torch.float64, device=self.device)
@@ -224,19 +273,33 @@ class TSDFVolume:
             return self.raycast_enqueue(_poses(c2w, self.device), K, H, W, near, far, step, min_weight, normals, color)
 
     def track(self, depth, K, pose_init, pose_ref=None, model: Optional[Raycast] = None, max_dist: Optional[float] = None,
-              max_iteration: int = 30, relative_fitness: float = 1e-6, relative_rmse: float = 1e-6, depth_max: float = math.inf) -> TrackResult:
+              max_iteration: int = 30, relative_fitness: float = 1e-6, relative_rmse: float = 1e-6, depth_max: float = math.inf,
+              rgb=None, color_weight: Optional[float] = None, max_color_diff: float = math.inf, relative_color_rmse: float = 1e-6):
         """The pose of the depth frame ``depth`` [H,W] by point-to-plane ICP against the volume's ray cast from ``pose_ref`` (by
         default ``pose_init``; or against ``model``, a one-view Raycast made from pose_ref), starting at ``pose_init``.  Pairs are
         found by projecting the live points into the model image and kept within ``max_dist`` (trunc by default).  No pyramid:
-        the capture range is a few centimetres and degrees.  One read-back."""
+        the capture range is a few centimetres and degrees.  One read-back.  -> TrackResult.
+        With ``rgb`` [H,W,3], the frame's colour, and a volume made with color=True, every pair whose projection falls into a 2 x 2
+        patch of model pixels also gives a photometric row -- the model's bilinear intensity against the live pixel's, weighted by
+        ``color_weight`` (DEFAULT_COLOR_WEIGHT unless given) and kept while its residual is within ``max_color_diff`` -- which holds
+        the pose where depth leaves it free: along a wall, along an edge.  -> ColorTrackResult."""
         with torch.cuda.device(self.device):
             D = _images(depth, self.device, 0, "depth")[0]
             P0 = _poses(pose_init, self.device)[0].contiguous()
             Pr = None if pose_ref is None else _poses(pose_ref, self.device)[0].contiguous()
-            result, pose = self.track_enqueue(D, K, P0, Pr, model, max_dist, max_iteration, relative_fitness, relative_rmse, depth_max)
-            got = torch.cat([result, pose.reshape(-1).to(torch.float64)]).cpu()
-        r = got[:20]
-        return TrackResult(got[20:].reshape(4, 4).to(torch.float32), r[:16].reshape(4, 4).clone(), int(r[16]), float(r[17]), float(r[18]), int(r[19]))
+            if rgb is None:
+                result, pose = self.track_enqueue(D, K, P0, Pr, model, max_dist, max_iteration, relative_fitness, relative_rmse, depth_max)
+            else:
+                C3 = _images(rgb, self.device, 3, "rgb")
+                if tuple(C3.shape) != (1,) + tuple(D.shape) + (3,):
+                    raise ValueError(f"rgb: expected {tuple(D.shape) + (3,)}, got {tuple(C3.shape[1:]) if C3.shape[0] == 1 else tuple(C3.shape)}")
+                result, pose = self.track_enqueue(D, K, P0, Pr, model, max_dist, max_iteration, relative_fitness, relative_rmse, depth_max,
+                                                  rgb=C3[0], color_weight=color_weight, max_color_diff=max_color_diff,
+                                                  relative_color_rmse=relative_color_rmse)
+            got = torch.cat([pose.reshape(-1).to(torch.float64), result]).cpu()
+        r = got[16:]
+        head = (got[:16].reshape(4, 4).to(torch.float32), r[:16].reshape(4, 4).clone(), int(r[16]), float(r[17]), float(r[18]), int(r[19]))
+        return TrackResult(*head) if rgb is None else ColorTrackResult(*head, int(r[20]), float(r[21]))
 
     def integrate(self, depth, c2w, K, rgb=None, depth_max: float = math.inf, views_per_call: Optional[int] = None) -> TSDFCounts:
         """Fuses the views in the order given.  depth [n,H,W] or [H,W] (0 = no measurement), c2w [n,4,4] or [4,4] (camera to world,
@@ -337,7 +400,7 @@ def tsdf_mesh_from_frames(depth, c2w, K, voxel_size: float, trunc: Optional[floa
 
 
 def tsdf_odometry(depth, K, first_pose, voxel_size: float, bounds, trunc: Optional[float] = None, rgb=None, min_correspondences: int = 0,
-                  device=None, **track_kw):
+                  device=None, color_weight: Optional[float] = None, **track_kw):
     """Frame-to-model depth odometry, the classical baseline's tracker: frame 0 is fused at ``first_pose``; every later frame is
     registered (TSDFVolume.track_enqueue, ``track_kw`` to it) against the ray cast from the previous frame's pose, starting from
     that pose, and fused at the pose found.  The walk is enqueued whole, the poses handed on between the stages on the device;
@@ -346,7 +409,11 @@ def tsdf_odometry(depth, K, first_pose, voxel_size: float, bounds, trunc: Option
     -> (poses fp32 [n,4,4] on the host, records, TSDFVolume); a record is a dict of transformation (float64 [4,4], the
     registration's pose before its rounding; zero for frame 0), n_correspondences, fitness, inlier_rmse, iterations and lost.
     Score the poses with ``trajectory_metrics(poses, gt_c2w)`` (aligned ATE); the first pose is given, so ``align=False``
-    measures the drift itself."""
+    measures the drift itself.
+    ``rgb`` [n,H,W,3] is fused with the depth; the registration uses it only when ``color_weight`` is given (TSDFVolume.track's
+    colour term), and the records then also hold n_color and color_rmse."""
+    if color_weight is not None and rgb is None:
+        raise ValueError("color_weight: tracking with colour needs rgb")
     voxel_size = float(voxel_size)
     trunc = 4.0 * voxel_size if trunc is None else float(trunc)
     dev = depth.device if torch.is_tensor(depth) and depth.is_cuda else _device(device)
@@ -360,21 +427,28 @@ def tsdf_odometry(depth, K, first_pose, voxel_size: float, bounds, trunc: Option
             raise ValueError("no frames")
         vol = TSDFVolume(b[:, 0], voxel_size, dims, trunc, color=C3 is not None, device=dev)
         poses = torch.empty(n, 4, 4, dtype=torch.float32, device=dev)
-        results = torch.zeros(n, _lib.TRACK_RESULT_DOUBLES, dtype=torch.float64, device=dev)
+        words = _lib.TRACK_RESULT_DOUBLES if color_weight is None else _lib.TRACK_COLOR_RESULT_DOUBLES
+        results = torch.zeros(n, words, dtype=torch.float64, device=dev)
         lost = torch.zeros(n, dtype=torch.bool, device=dev)
         poses[0] = _poses(first_pose, dev)[0]
         nan_pose = torch.full((4, 4), math.nan, dtype=torch.float32, device=dev)
         vol.integrate_enqueue(D[:1], poses[:1], K, None if C3 is None else C3[:1])
         for k in range(1, n):
             prev = poses[k - 1]
-            result, pose = vol.track_enqueue(D[k], K, prev, **track_kw)
+            if color_weight is None:
+                result, pose = vol.track_enqueue(D[k], K, prev, **track_kw)
+            else:
+                result, pose = vol.track_enqueue(D[k], K, prev, rgb=C3[k], color_weight=color_weight, **track_kw)
             bad = result[16] < float(min_correspondences)
             poses[k] = torch.where(bad, prev, pose)
             results[k], lost[k] = result, bad
             vol.integrate_enqueue(D[k:k + 1], torch.where(bad, nan_pose, pose)[None], K, None if C3 is None else C3[k:k + 1])
         got = torch.cat([poses.reshape(n, 16).to(torch.float64), results, lost[:, None].to(torch.float64)], 1).cpu()
     records = [{"transformation": r[16:32].reshape(4, 4).clone(), "n_correspondences": int(r[32]), "fitness": float(r[33]),
-                "inlier_rmse": float(r[34]), "iterations": int(r[35]), "lost": bool(r[36])} for r in got]
+                "inlier_rmse": float(r[34]), "iterations": int(r[35]), "lost": bool(r[-1])} for r in got]
+    if color_weight is not None:
+        for rec, r in zip(records, got):
+            rec["n_color"], rec["color_rmse"] = int(r[36]), float(r[37])
     return got[:, :16].reshape(n, 4, 4).to(torch.float32), records, vol
 
 

@@ -8,6 +8,10 @@ Milliseconds between two events on the stream after one warm-up call, median of 
                               every sample evaluated (MIPSF_TRACK_NO_SKIP); rays per second are pixels over the time of the call
   register_10                 mipsf_track_register against one ray-cast view from a pose 2 degrees and 5 cm away, max_iteration 10,
                               relative_fitness = relative_rmse = 0 so that all 11 evaluations run
+  register_color_10           mipsf_track_register_color on the same frame and pose against one view, cast with its
+                              colour, of a second volume that fused the same views with the box room's texture 0.5 + 0.5 sin(4 x);
+                              max_iteration 10 and relative_color_rmse = 0 as well, so that all 11 evaluations run; in the same run as
+                              register_10, to be read beside it
   odometry_frame              what tsdf_odometry enqueues per frame: ray cast, registration (30 iterations at most, the default
                               stop), the selection of the pose and the fusion of the frame
   volume_march_render         the route to the same depth image without the ray caster: volume(), marching_cubes, render_mesh_depth
@@ -46,6 +50,18 @@ def timed3(fn, reps, setup=None):
         if k:
             out.append(a.elapsed_time(b))
     return [round(float(np.median(out)), 4), round(float(min(out)), 4), round(float(max(out)), 4)]
+
+
+def texture(depth, poses, K):
+    """the box room's texture at the points a depth image sees: depth [n,H,W], poses [n,4,4] on the device -> rgb fp32 [n,H,W,3]"""
+    n, H, W = depth.shape
+    fx, fy, cx, cy = K
+    row, col = torch.meshgrid(torch.arange(H, device=depth.device, dtype=torch.float32), torch.arange(W, device=depth.device, dtype=torch.float32),
+                              indexing="ij")
+    d_cam = torch.stack([(col - cx) / fx, -(row - cy) / fy, -torch.ones_like(col)], -1)
+    d_world = torch.einsum("nrc,hwc->nhwr", poses[:, :3, :3], d_cam)
+    hit = poses[:, None, None, :3, 3] + d_world * depth[..., None]
+    return (0.5 + 0.5 * torch.sin(4.0 * hit)).contiguous()
 
 
 def main():
@@ -96,6 +112,22 @@ def main():
         r = result.cpu().numpy()
         run["register_10"] = {"iterations": int(r[19]), "pairs": int(r[16]), "fitness": round(float(r[17]), 4), "rmse_m": round(float(r[18]), 5),
                               "translation_error_cm": round(100 * float((pose[:3, 3] - away[:3, 3]).norm()), 3)}
+        # the same registration with the colour term, against a volume that fused the texture too
+        cvol = tsdf.TSDFVolume(origin, voxel, dims, 4 * voxel, color=True, device=dev)
+        for k in range(0, args.views, 16):                       # the colour images of 16 views at a time
+            cvol.integrate_enqueue(depth[k:k + 16], poses[k:k + 16], K, texture(depth[k:k + 16], poses[k:k + 16], K))
+        cmodel = cvol.raycast_enqueue(poses[1:2], K, H, W, color=True)
+        rgb = texture(live, away[None], K)[0]
+        ckw = dict(max_iteration=10, relative_fitness=0.0, relative_rmse=0.0, relative_color_rmse=0.0, rgb=rgb)
+        run["register_color_10_ms"] = timed3(lambda: cvol.track_enqueue(live[0], K, poses[1], poses[1], cmodel, **ckw), args.reps)
+        run["register_10_again_ms"] = timed3(lambda: vol.track_enqueue(live[0], K, poses[1], poses[1], model, max_iteration=10, relative_fitness=0.0,
+                                                                       relative_rmse=0.0), args.reps)
+        result, pose = cvol.track_enqueue(live[0], K, poses[1], poses[1], cmodel, **ckw)
+        r = result.cpu().numpy()
+        run["register_color_10"] = {"iterations": int(r[19]), "pairs": int(r[16]), "fitness": round(float(r[17]), 4), "rmse_m": round(float(r[18]), 5),
+                                    "rows": int(r[20]), "color_rmse": round(float(r[21]), 5), "color_weight": tsdf.DEFAULT_COLOR_WEIGHT,
+                                    "translation_error_cm": round(100 * float((pose[:3, 3] - away[:3, 3]).norm()), 3)}
+        del cvol, cmodel
         nan_pose = torch.full((4, 4), float("nan"), device=dev)
 
         def frame():
