@@ -23,6 +23,7 @@
 // Roofline: MFMA-bound.  72 370 FLOP/sample forward, 217 110 forward+backward; the three big layers
 // are 138 k-steps x 4 row tiles = 552 MFMAs (64 cycles each) per 32 samples forward.
 #include "decoder_dev.h"
+#include "launch.h"
 
 namespace mipsf {
 using namespace dl;
@@ -1032,40 +1033,22 @@ static int decoder_fwd_launch(const float* packed, const float* feat, int feat_l
     if (cus <= 0) return 3;
     // persistent LDS-resident weights pay off once every CU has several rounds of tiles to amortise the 140 KB fill
     const bool persistent = n_tiles >= (uint32_t)cus * 8u * MIPSF_FWD_LDS_MIN_ROUNDS;
-#define FWD(PE, LAY, SV, SDF)                                                                                    \
-    do {                                                                                                         \
-        if (persistent) {                                                                                        \
-            static bool attr_set_dev[MAX_DEVICES] = {false};                                                     \
-            bool& attr_set = attr_set_dev[device_slot()];                                                        \
-            if (!attr_set) {                                                                                     \
-                if (hipFuncSetAttribute((const void*)decoder_fwd_lds_kernel<PE, LAY, SV, SDF>,                   \
-                                        hipFuncAttributeMaxDynamicSharedMemorySize, FWD_LDS_BYTES) != hipSuccess) { \
-                    set_error("cannot raise dynamic LDS to %d bytes", FWD_LDS_BYTES);                            \
-                    return 4;                                                                                    \
-                }                                                                                                \
-                attr_set = true;                                                                                 \
-            }                                                                                                    \
-            hipLaunchKernelGGL((decoder_fwd_lds_kernel<PE, LAY, SV, SDF>), dim3(cus), dim3(FWD_LDS_BLOCK), FWD_LDS_BYTES, s, \
-                               packed, feat, x, embed_pos, out, saved, M, 0, n_tiles);                           \
-        } else {                                                                                                 \
-            hipLaunchKernelGGL((decoder_fwd_kernel<PE, LAY, SV, SDF>), dim3(blocks), dim3(DEC_BLOCK), 0, s, packed, feat, x, \
-                               embed_pos, out, saved, M, 0);                                                     \
-        }                                                                                                        \
-    } while (0)
-#define FWD_SV(PE, LAY)                                  \
-    do {                                                 \
-        if (sdf_only) FWD(PE, LAY, false, true);         \
-        else if (saved != nullptr) FWD(PE, LAY, true, false); \
-        else FWD(PE, LAY, false, false);                 \
-    } while (0)
-    if (pe_mode == 0) {
-        if (feat_layout == MIPSF_FEAT_AOS) FWD_SV(true, MIPSF_FEAT_AOS); else FWD_SV(true, MIPSF_FEAT_LEVEL_MAJOR);
-    } else {
-        if (feat_layout == MIPSF_FEAT_AOS) FWD_SV(false, MIPSF_FEAT_AOS); else FWD_SV(false, MIPSF_FEAT_LEVEL_MAJOR);
-    }
-#undef FWD_SV
-#undef FWD
-    return check_launch("decoder_fwd");
+    return with_bool(pe_mode == 0, [&](auto PE) { return with_layout(feat_layout, [&](auto LAY) {
+        auto arm = [&](auto SAVE, auto SDF) {
+            if (persistent) {
+                constexpr auto kern = decoder_fwd_lds_kernel<PE.value, LAY.value, SAVE.value, SDF.value>;
+                if (!grant_lds<kern>(FWD_LDS_BYTES)) return lds_refused(FWD_LDS_BYTES);
+                hipLaunchKernelGGL(kern, dim3(cus), dim3(FWD_LDS_BLOCK), FWD_LDS_BYTES, s, packed, feat, x, embed_pos, out, saved,
+                                   M, 0, n_tiles);
+            } else {
+                hipLaunchKernelGGL((decoder_fwd_kernel<PE.value, LAY.value, SAVE.value, SDF.value>), dim3(blocks), dim3(DEC_BLOCK), 0,
+                                   s, packed, feat, x, embed_pos, out, saved, M, 0);
+            }
+            return check_launch("decoder_fwd");
+        };
+        // (SAVE, SDF): the SDF-only forward, the forward that keeps its activations, the plain one
+        return sdf_only ? arm(no, yes) : saved != nullptr ? arm(yes, no) : arm(no, no);
+    }); });
 }
 
 int mipsf_decoder_fwd(const float* packed, const float* feat, int feat_layout, const float* x,
@@ -1088,12 +1071,11 @@ int mipsf_decoder_bwd_chain(const float* packed, int feat_layout, const float* x
     hipStream_t s = (hipStream_t)stream;
     const uint32_t blocks = (uint32_t)((n_wave_tiles(M) + 3) / 4);
     float* dsmall = dact + n_block_tiles(M) * 4 * ACT_TILE_FLOATS;
-#define BWD(PE, LAY) \
-    hipLaunchKernelGGL((decoder_bwd_lds_kernel<PE, LAY>), dim3(blocks), dim3(DEC_BLOCK), 0, s, packed, x, out, dout, saved, dfeat, dx, dembed_pos, dact, dsmall, M, MIPSF_PIN_ARG)
-    if (pe_mode == 0) { if (feat_layout == MIPSF_FEAT_AOS) BWD(true, MIPSF_FEAT_AOS); else BWD(true, MIPSF_FEAT_LEVEL_MAJOR); }
-    else { if (feat_layout == MIPSF_FEAT_AOS) BWD(false, MIPSF_FEAT_AOS); else BWD(false, MIPSF_FEAT_LEVEL_MAJOR); }
-#undef BWD
-    return check_launch("decoder_bwd_chain");
+    return with_bool(pe_mode == 0, [&](auto PE) { return with_layout(feat_layout, [&](auto LAY) {
+        hipLaunchKernelGGL((decoder_bwd_lds_kernel<PE.value, LAY.value>), dim3(blocks), dim3(DEC_BLOCK), 0, s, packed, x, out, dout,
+                           saved, dfeat, dx, dembed_pos, dact, dsmall, M, MIPSF_PIN_ARG);
+        return check_launch("decoder_bwd_chain");
+    }); });
 }
 
 static int decoder_wgrad_launch(const float* feat, int feat_layout, const float* x, const float* embed_pos, int pe_mode,
@@ -1125,27 +1107,16 @@ static int decoder_wgrad_launch(const float* feat, int feat_layout, const float*
     if (cus <= 0) return 3;
     uint32_t wg_blocks = n_bt < (uint32_t)cus ? n_bt : (uint32_t)cus;
     if (wg_blocks > WG_MAX_BLOCKS) wg_blocks = WG_MAX_BLOCKS;
-#define WG(PE, LAY, BF)                                                                                          \
-    do {                                                                                                         \
-        static bool attr_set_dev[MAX_DEVICES] = {false};                                                         \
-        bool& attr_set = attr_set_dev[device_slot()];                                                            \
-        if (!attr_set) {                                                                                         \
-            if (hipFuncSetAttribute((const void*)decoder_wgrad_kernel<PE, LAY, BF>,                              \
-                                    hipFuncAttributeMaxDynamicSharedMemorySize, WG_LDS_BYTES) != hipSuccess) {   \
-                set_error("cannot raise dynamic LDS to %d bytes", WG_LDS_BYTES);                                 \
-                return 4;                                                                                        \
-            }                                                                                                    \
-            attr_set = true;                                                                                     \
-        }                                                                                                        \
-        hipLaunchKernelGGL((decoder_wgrad_kernel<PE, LAY, BF>), dim3(wg_blocks), dim3(DEC_BLOCK), WG_LDS_BYTES, s, \
-                           feat, x, embed_pos, saved, dact, dsmall, partial, M, n_bt);                           \
-    } while (0)
-#define WG_P(PE, LAY) do { if (bf16x3) WG(PE, LAY, true); else WG(PE, LAY, false); } while (0)
-    if (pe_mode == 0) { if (feat_layout == MIPSF_FEAT_AOS) WG_P(true, MIPSF_FEAT_AOS); else WG_P(true, MIPSF_FEAT_LEVEL_MAJOR); }
-    else { if (feat_layout == MIPSF_FEAT_AOS) WG_P(false, MIPSF_FEAT_AOS); else WG_P(false, MIPSF_FEAT_LEVEL_MAJOR); }
-#undef WG_P
-#undef WG
-    if (int e = check_launch("decoder_wgrad")) return e;
+    const int rc = with_bool(pe_mode == 0, [&](auto PE) { return with_layout(feat_layout, [&](auto LAY) {
+        return with_bool(bf16x3, [&](auto BF) {
+            constexpr auto kern = decoder_wgrad_kernel<PE.value, LAY.value, BF.value>;
+            if (!grant_lds<kern>(WG_LDS_BYTES)) return lds_refused(WG_LDS_BYTES);
+            hipLaunchKernelGGL(kern, dim3(wg_blocks), dim3(DEC_BLOCK), WG_LDS_BYTES, s, feat, x, embed_pos, saved, dact, dsmall,
+                               partial, M, n_bt);
+            return check_launch("decoder_wgrad");
+        });
+    }); });
+    if (rc) return rc;
     hipLaunchKernelGGL(decoder_wgrad_reduce_kernel, dim3((G_TOTAL + 255) / 256, WG_REDUCE_SLICES), dim3(256), 0, s, partial, wg_blocks, g);
     return check_launch("decoder_wgrad_reduce");
 }

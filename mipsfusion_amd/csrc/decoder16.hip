@@ -23,6 +23,7 @@
 // Where the operand planes live: planes 0 and 1 of the weight images in LDS (persistent kernels: 152 / 160 KB), plane 2 of
 // the bf16 mode (used by ONE of the six products) in L2, requested five product groups ahead of its use.
 #include "decoder_dev.h"
+#include "launch.h"
 #include <stdlib.h>
 
 namespace mipsf {
@@ -1392,13 +1393,11 @@ int mipsf_decoder_pack16(const mipsf_decoder_weights* w, float* packed16, int pr
                   "precision must be f16x3, f16 or bf16x6");
     static_assert(IMG16H_HALVES >= HEAD16_HALVES && IMG16H_HALVES >= IMG16B_HALVES, "one thread per hi-image element covers all");
     static_assert(f16_lds_bytes<2>() <= 160 * 1024, "tail + both image sets must fit the 160 KB of LDS of a CU");
-    if (precision == MIPSF_PREC_BF16X6)
-        hipLaunchKernelGGL(decoder_pack16_kernel<3>, dim3((IMG16H_HALVES + 255) / 256), dim3(256), 0, (hipStream_t)stream,
-                           to_w16(*w), packed16);
-    else
-        hipLaunchKernelGGL(decoder_pack16_kernel<2>, dim3((IMG16H_HALVES + 255) / 256), dim3(256), 0, (hipStream_t)stream,
-                           to_w16(*w), packed16);
-    return check_launch("decoder_pack16");
+    return with_bool(precision == MIPSF_PREC_BF16X6, [&](auto BF) {
+        hipLaunchKernelGGL(decoder_pack16_kernel<BF.value ? 3 : 2>, dim3((IMG16H_HALVES + 255) / 256), dim3(256), 0,
+                           (hipStream_t)stream, to_w16(*w), packed16);
+        return check_launch("decoder_pack16");
+    });
 }
 
 // tile_live_clear (optional): the live-tile buffer the backward chain of THIS forward will fill
@@ -1431,48 +1430,31 @@ int mipsf_decoder_fwd16(const mipsf_decoder_fwd16_args* a, void* stream) {
     const bool persistent = n_tiles >= (uint32_t)cus * persist_min_tiles_per_cu();
     const char* st_env = getenv("MIPSF_F16_STAGGER");
     const int stagger = st_env ? atoi(st_env) : 0;
-#define F16(LAY, SV, SDF, SPL)                                                                                     \
-    do {                                                                                                           \
-        if (persistent) {                                                                                          \
-            static bool attr_set_dev[MAX_DEVICES] = {false};                                                       \
-            bool& attr_set = attr_set_dev[device_slot()];                                                          \
-            if (!attr_set) {                                                                                       \
-                if (hipFuncSetAttribute((const void*)decoder16_fwd_lds_kernel<LAY, SV, SDF, SPL>,                  \
-                                        hipFuncAttributeMaxDynamicSharedMemorySize, f16_lds_bytes<SPL>()) !=       \
-                    hipSuccess) {                                                                                  \
-                    set_error("cannot raise dynamic LDS to %d bytes", f16_lds_bytes<SPL>());                       \
-                    return 4;                                                                                      \
-                }                                                                                                  \
-                attr_set = true;                                                                                   \
-            }                                                                                                      \
-            hipLaunchKernelGGL((decoder16_fwd_lds_kernel<LAY, SV, SDF, SPL>), dim3(cus), dim3(F16_LDS_BLOCK),      \
-                               f16_lds_bytes<SPL>(), s, packed16, feat, x, out, saved, M, stagger << 8, n_tiles,   \
-                               clear_hdr);                                                                         \
-        } else {                                                                                                   \
-            hipLaunchKernelGGL((decoder16_fwd_kernel<LAY, SV, SDF, SPL>), dim3(blocks), dim3(DEC_BLOCK), 0, s,     \
-                               packed16, feat, x, out, saved, M, 0, clear_hdr);                                    \
-        }                                                                                                          \
-    } while (0)
-#define F16_MODE(LAY, SPL, SPLS)                            \
-    do {                                                    \
-        if (sdf_only) F16(LAY, 0, true, SPL);               \
-        else if (saved != nullptr && lean_record == 2) F16(LAY, 3, false, SPLS); \
-        else if (saved != nullptr && lean_record) F16(LAY, 2, false, SPLS); \
-        else if (saved != nullptr) F16(LAY, 1, false, SPL); \
-        else F16(LAY, 0, false, SPL);                       \
-    } while (0)
-    if (feat_layout == MIPSF_FEAT_AOS) {
-        if (precision == MIPSF_PREC_BF16X6) F16_MODE(MIPSF_FEAT_AOS, 3, 3);
-        else if (precision == MIPSF_PREC_F16X3) F16_MODE(MIPSF_FEAT_AOS, 2, 2);
-        else F16_MODE(MIPSF_FEAT_AOS, 1, 2);
-    } else {
-        if (precision == MIPSF_PREC_BF16X6) F16_MODE(MIPSF_FEAT_LEVEL_MAJOR, 3, 3);
-        else if (precision == MIPSF_PREC_F16X3) F16_MODE(MIPSF_FEAT_LEVEL_MAJOR, 2, 2);
-        else F16_MODE(MIPSF_FEAT_LEVEL_MAJOR, 1, 2);
-    }
-#undef F16_MODE
-#undef F16
-    return check_launch("decoder_fwd16");
+    // weight planes of the arithmetic: bf16x6 3, f16x3 2, f16 1
+    const int planes = precision == MIPSF_PREC_BF16X6 ? 3 : precision == MIPSF_PREC_F16X3 ? 2 : 1;
+    return with_layout(feat_layout, [&](auto LAY) { return with_int<1, 2, 3>(planes, [&](auto NP) {
+        auto arm = [&](auto SV, auto SDF, auto PLANES) {
+            constexpr int lds = f16_lds_bytes<PLANES.value>();
+            if (persistent) {
+                constexpr auto kern = decoder16_fwd_lds_kernel<LAY.value, SV.value, SDF.value, PLANES.value>;
+                if (!grant_lds<kern>(lds)) return lds_refused(lds);
+                hipLaunchKernelGGL(kern, dim3(cus), dim3(F16_LDS_BLOCK), lds, s, packed16, feat, x, out, saved, M, stagger << 8,
+                                   n_tiles, clear_hdr);
+            } else {
+                hipLaunchKernelGGL((decoder16_fwd_kernel<LAY.value, SV.value, SDF.value, PLANES.value>), dim3(blocks), dim3(DEC_BLOCK),
+                                   0, s, packed16, feat, x, out, saved, M, 0, clear_hdr);
+            }
+            return check_launch("decoder_fwd16");
+        };
+        // (save mode, SDF only, planes): save mode 0 keeps nothing, 1 the full record, 2 and 3 the lean records, which the
+        // kernels of two planes at the least write
+        constexpr int_tag<(NP.value < 2 ? 2 : NP.value)> NP_LEAN;
+        if (sdf_only) return arm(int_tag<0>{}, yes, NP);
+        if (saved != nullptr && lean_record == 2) return arm(int_tag<3>{}, no, NP_LEAN);
+        if (saved != nullptr && lean_record) return arm(int_tag<2>{}, no, NP_LEAN);
+        if (saved != nullptr) return arm(int_tag<1>{}, no, NP);
+        return arm(int_tag<0>{}, no, NP);
+    }); });
 }
 
 
@@ -1515,39 +1497,19 @@ int mipsf_decoder_bwd_chain16(const mipsf_decoder_chain16_args* a, void* stream)
         set_error("cannot clear the tile counters");
         return 4;
     }
-#define B16(LAY, NPL)                                                                                              \
-    do {                                                                                                           \
-        if (live_list) B16C(LAY, NPL, true); else B16C(LAY, NPL, false);                                           \
-    } while (0)
-#define B16C(LAY, NPL, CMP)                                                                                        \
-    do {                                                                                                           \
-        if (persistent) {                                                                                          \
-            static bool attr_set_dev[MAX_DEVICES] = {false};                                                       \
-            bool& attr_set = attr_set_dev[device_slot()];                                                          \
-            if (!attr_set) {                                                                                       \
-                if (hipFuncSetAttribute((const void*)decoder16_bwd_lds_kernel<LAY, NPL, CMP>,                          \
-                                        hipFuncAttributeMaxDynamicSharedMemorySize, B16_LDS_BYTES) != hipSuccess) { \
-                    set_error("cannot raise dynamic LDS to %d bytes", B16_LDS_BYTES);                              \
-                    return 4;                                                                                      \
-                }                                                                                                  \
-                attr_set = true;                                                                                   \
-            }                                                                                                      \
-            hipLaunchKernelGGL((decoder16_bwd_lds_kernel<LAY, NPL, CMP>), dim3(cus), dim3(F16_LDS_BLOCK), B16_LDS_BYTES, s, \
-                               packed16, x, out, dout, saved, dfeat, dx, dact, dsmall, M, n_tiles, tile_live,      \
-                               lean_dact, live_list);                                                              \
-        } else {                                                                                                   \
-            hipLaunchKernelGGL((decoder16_bwd_kernel<LAY, NPL, CMP>), dim3(blocks), dim3(DEC_BLOCK), 0, s, packed16, x, out, \
-                               dout, saved, dfeat, dx, dact, dsmall, M, tile_live, lean_dact, live_list);          \
-        }                                                                                                          \
-    } while (0)
-    if (feat_layout == MIPSF_FEAT_AOS) {
-        if (bf) B16(MIPSF_FEAT_AOS, 3); else B16(MIPSF_FEAT_AOS, 2);
-    } else {
-        if (bf) B16(MIPSF_FEAT_LEVEL_MAJOR, 3); else B16(MIPSF_FEAT_LEVEL_MAJOR, 2);
-    }
-#undef B16
-#undef B16C
-    return check_launch("decoder_bwd_chain16");
+    return with_layout(feat_layout, [&](auto LAY) { return with_bool(bf, [&](auto BF) { return with_bool(live_list != nullptr, [&](auto CMP) {
+        constexpr int NP = BF.value ? 3 : 2;
+        if (persistent) {
+            constexpr auto kern = decoder16_bwd_lds_kernel<LAY.value, NP, CMP.value>;
+            if (!grant_lds<kern>(B16_LDS_BYTES)) return lds_refused(B16_LDS_BYTES);
+            hipLaunchKernelGGL(kern, dim3(cus), dim3(F16_LDS_BLOCK), B16_LDS_BYTES, s, packed16, x, out, dout, saved, dfeat, dx, dact,
+                               dsmall, M, n_tiles, tile_live, lean_dact, live_list);
+        } else {
+            hipLaunchKernelGGL((decoder16_bwd_kernel<LAY.value, NP, CMP.value>), dim3(blocks), dim3(DEC_BLOCK), 0, s, packed16, x, out,
+                               dout, saved, dfeat, dx, dact, dsmall, M, tile_live, lean_dact, live_list);
+        }
+        return check_launch("decoder_bwd_chain16");
+    }); }); });
 }
 
 int mipsf_decoder_live_compact(const float* dout, uint32_t M, uint32_t* live_list, float* dfeat, float* dx, int feat_layout,
@@ -1564,12 +1526,11 @@ int mipsf_decoder_live_compact(const float* dout, uint32_t M, uint32_t* live_lis
     }
     MIPSF_REQUIRE(dout && dfeat && dx, "null pointer");
     const uint32_t blocks = lc_blocks(M);
-    if (feat_layout == MIPSF_FEAT_AOS)
-        hipLaunchKernelGGL(live_flag_kernel<MIPSF_FEAT_AOS>, dim3(blocks), dim3(LC_BLOCK), 0, s, dout, M, live_list, dfeat, dx);
-    else
-        hipLaunchKernelGGL(live_flag_kernel<MIPSF_FEAT_LEVEL_MAJOR>, dim3(blocks), dim3(LC_BLOCK), 0, s, dout, M, live_list, dfeat, dx);
-    hipLaunchKernelGGL(live_list_kernel, dim3(blocks), dim3(LC_BLOCK), 0, s, M, live_list);
-    return check_launch("decoder_live_compact");
+    return with_layout(feat_layout, [&](auto LAY) {
+        hipLaunchKernelGGL(live_flag_kernel<LAY.value>, dim3(blocks), dim3(LC_BLOCK), 0, s, dout, M, live_list, dfeat, dx);
+        hipLaunchKernelGGL(live_list_kernel, dim3(blocks), dim3(LC_BLOCK), 0, s, M, live_list);
+        return check_launch("decoder_live_compact");
+    });
 }
 
 }  // extern "C"

@@ -11,6 +11,7 @@
 // XCD k serves levels {k+8, k} one after the other (fine level first), which keeps each L2 filled with
 // one level's table instead of thrashing all 34 MiB through every L2.  The mapping only affects speed.
 #include "common.h"
+#include "launch.h"
 #include "decoder_layout.h"      // layout of the backward chain's live-tile lists (mipsf_hashgrid_dx_from_jac)
 
 namespace mipsf {
@@ -1602,6 +1603,22 @@ uint64_t hashgrid_det_scratch_floats(const mipsf_grid_meta* meta, uint32_t M, in
     return p.w_end + (need_dx ? (uint64_t)g.n_levels * M * 3 : 0) + 64;
 }
 
+// dL/dx: per-level partials in dxl, summed in level order into dx (fixed-order; the deterministic and the fast path share it)
+static int launch_dx(const float* x, const float* params, const float* dout, float* dxl, float* dx, uint32_t M, const GridLevels& g,
+                     int layout, hipStream_t s) {
+    uint32_t nchunk;
+    const uint32_t nb = grid_blocks(M, g.n_levels, nchunk);
+    const float2* table = reinterpret_cast<const float2*>(params);
+    const int rc = with_layout(layout, [&](auto LAY) {
+        hipLaunchKernelGGL(hashgrid_dx_kernel<LAY.value>, dim3(nb), dim3(HG_BLOCK), 0, s, x, table, dout, dxl, M, g, nchunk);
+        return check_launch("hashgrid_dx");
+    });
+    if (rc) return rc;
+    const uint64_t n3 = (uint64_t)M * 3;
+    hipLaunchKernelGGL(hashgrid_dx_reduce_kernel, dim3((uint32_t)((n3 + 255) / 256)), dim3(256), 0, s, dxl, dx, n3, g.n_levels);
+    return check_launch("hashgrid_dx_reduce");
+}
+
 static int hashgrid_bwd_det(const float* x, const float* params, const float* dout, float* dparams, float* dx, float* scratch,
                             uint32_t M, const mipsf_grid_meta* meta, int layout, bool fresh, void* stream) {
     GridLevels g;
@@ -1622,11 +1639,11 @@ static int hashgrid_bwd_det(const float* x, const float* params, const float* do
         uint32_t *cnt = ws + p.o_cnt, *tot = ws + p.o_tot, *start = ws + p.o_start;
         double2* psum = reinterpret_cast<double2*>(scratch);
         const dim3 eg((M + DET_BLOCK - 1) / DET_BLOCK, g.n_levels);
-        if (layout == MIPSF_FEAT_AOS)
-            hipLaunchKernelGGL(det_emit_kernel<MIPSF_FEAT_AOS>, eg, dim3(DET_BLOCK), 0, s, x, dout, keys[0], M, g, p.dead);
-        else
-            hipLaunchKernelGGL(det_emit_kernel<MIPSF_FEAT_LEVEL_MAJOR>, eg, dim3(DET_BLOCK), 0, s, x, dout, keys[0], M, g, p.dead);
-        if (int e = check_launch("hashgrid_det_emit")) return e;
+        int rc = with_layout(layout, [&](auto LAY) {
+            hipLaunchKernelGGL(det_emit_kernel<LAY.value>, eg, dim3(DET_BLOCK), 0, s, x, dout, keys[0], M, g, p.dead);
+            return check_launch("hashgrid_det_emit");
+        });
+        if (rc) return rc;
         for (uint32_t pass = 0; pass < p.passes; ++pass) {
             const uint32_t a = pass & 1u, shift = 8u * pass;
             hipLaunchKernelGGL(det_count_kernel, dim3(nb), dim3(DET_BLOCK), 0, s, keys[a], cnt, n, nb, shift);
@@ -1639,31 +1656,15 @@ static int hashgrid_bwd_det(const float* x, const float* params, const float* do
         const uint32_t* sv = vals[p.passes & 1u];
         const uint32_t tb = (uint32_t)((p.n + DET_BLOCK - 1) / DET_BLOCK);
         hipLaunchKernelGGL(det_start_kernel, dim3(tb), dim3(DET_BLOCK), 0, s, sk, start, n, p.dead);
-#define DET_SUMS(LAY)                                                                                                    \
-    do {                                                                                                                 \
-        hipLaunchKernelGGL(det_pieces_kernel<LAY>, dim3(tb), dim3(DET_BLOCK), 0, s, x, dout, sk, sv, start, psum, n, M, g, \
-                           p.dead);                                                                                      \
-        hipLaunchKernelGGL(det_total_kernel<LAY>, dim3(tb), dim3(DET_BLOCK), 0, s, x, dout, sk, sv, psum, dparams, n, M, g, \
-                           p.dead, fresh ? 1u : 0u);                                                                     \
-    } while (0)
-        if (layout == MIPSF_FEAT_AOS) DET_SUMS(MIPSF_FEAT_AOS); else DET_SUMS(MIPSF_FEAT_LEVEL_MAJOR);
-#undef DET_SUMS
-        if (int e = check_launch("hashgrid_det_sums")) return e;
+        rc = with_layout(layout, [&](auto LAY) {
+            hipLaunchKernelGGL(det_pieces_kernel<LAY.value>, dim3(tb), dim3(DET_BLOCK), 0, s, x, dout, sk, sv, start, psum, n, M, g, p.dead);
+            hipLaunchKernelGGL(det_total_kernel<LAY.value>, dim3(tb), dim3(DET_BLOCK), 0, s, x, dout, sk, sv, psum, dparams, n, M, g, p.dead,
+                               fresh ? 1u : 0u);
+            return check_launch("hashgrid_det_sums");
+        });
+        if (rc) return rc;
     }
-    if (dx) {      // the fast path's dL/dx kernels (already fixed-order: per-level partials summed in level order)
-        float* dxl = scratch + p.o_dxl;
-        uint32_t nchunk;
-        const uint32_t nb = grid_blocks(M, g.n_levels, nchunk);
-        const float2* table = reinterpret_cast<const float2*>(params);
-        if (layout == MIPSF_FEAT_AOS)
-            hipLaunchKernelGGL(hashgrid_dx_kernel<MIPSF_FEAT_AOS>, dim3(nb), dim3(HG_BLOCK), 0, s, x, table, dout, dxl, M, g, nchunk);
-        else
-            hipLaunchKernelGGL(hashgrid_dx_kernel<MIPSF_FEAT_LEVEL_MAJOR>, dim3(nb), dim3(HG_BLOCK), 0, s, x, table, dout, dxl, M, g, nchunk);
-        if (int e = check_launch("hashgrid_dx")) return e;
-        const uint64_t n3 = (uint64_t)M * 3;
-        hipLaunchKernelGGL(hashgrid_dx_reduce_kernel, dim3((uint32_t)((n3 + 255) / 256)), dim3(256), 0, s, dxl, dx, n3, g.n_levels);
-        if (int e = check_launch("hashgrid_dx_reduce")) return e;
-    }
+    if (dx) return launch_dx(x, params, dout, scratch + p.o_dxl, dx, M, g, layout, s);      // (the fast path's, already fixed-order)
     return 0;
 }
 
@@ -1691,11 +1692,11 @@ static int hashgrid_fwd_impl(const float* x, const float* params, float* out, fl
     const uint32_t nb = grid_blocks(M, g.n_levels, nchunk);
     hipStream_t s = (hipStream_t)stream;
     const float2* table = reinterpret_cast<const float2*>(params);
-#define FWD(LAY, J) hipLaunchKernelGGL((hashgrid_fwd_kernel<LAY, J>), dim3(nb), dim3(HG_BLOCK), 0, s, x, table, out, jac, M, g, nchunk, ray_mask, S)
-    if (layout == MIPSF_FEAT_AOS) { if (jac) FWD(MIPSF_FEAT_AOS, true); else FWD(MIPSF_FEAT_AOS, false); }
-    else { if (jac) FWD(MIPSF_FEAT_LEVEL_MAJOR, true); else FWD(MIPSF_FEAT_LEVEL_MAJOR, false); }
-#undef FWD
-    return check_launch("hashgrid_fwd");
+    return with_layout(layout, [&](auto LAY) { return with_bool(jac != nullptr, [&](auto JAC) {
+        hipLaunchKernelGGL((hashgrid_fwd_kernel<LAY.value, JAC.value>), dim3(nb), dim3(HG_BLOCK), 0, s, x, table, out, jac, M, g, nchunk,
+                           ray_mask, S);
+        return check_launch("hashgrid_fwd");
+    }); });
 }
 
 int mipsf_hashgrid_fwd(const float* x, const float* params, float* out, float* jac, uint32_t M,
@@ -1717,11 +1718,11 @@ static int dx_from_jac(const float* jac, const float* dout, float* dx, const uin
     MIPSF_REQUIRE(!(tile_live && live_list), "tile_live and live_list are alternatives");
     if (int rc = check_ray_mask(ray_mask, S, M)) return rc;
     hipStream_t s = (hipStream_t)stream;
-    if (layout == MIPSF_FEAT_AOS)
-        hipLaunchKernelGGL(hashgrid_dx_jac_kernel<MIPSF_FEAT_AOS>, dim3((M + 255) / 256), dim3(256), 0, s, jac, dout, dx, M, g.n_levels, tile_live, live_list, ray_mask, S);
-    else
-        hipLaunchKernelGGL(hashgrid_dx_jac_kernel<MIPSF_FEAT_LEVEL_MAJOR>, dim3((M + 255) / 256), dim3(256), 0, s, jac, dout, dx, M, g.n_levels, tile_live, live_list, ray_mask, S);
-    return check_launch("hashgrid_dx_from_jac");
+    return with_layout(layout, [&](auto LAY) {
+        hipLaunchKernelGGL(hashgrid_dx_jac_kernel<LAY.value>, dim3((M + 255) / 256), dim3(256), 0, s, jac, dout, dx, M, g.n_levels,
+                           tile_live, live_list, ray_mask, S);
+        return check_launch("hashgrid_dx_from_jac");
+    });
 }
 int mipsf_hashgrid_dx_from_jac_masked(const float* jac, const float* dout, float* dx, const uint32_t* tile_live,
                                       const uint32_t* live_list, const uint32_t* ray_mask, uint32_t S, uint32_t M,
@@ -1804,11 +1805,10 @@ static int launch_route(const float* x, const float* dout, int layout, uint32_t*
         hipLaunchKernelGGL(scatter_zero_kernel, dim3((nz + 255) / 256), dim3(256), 0, s, cw, nz);
     }
     const uint32_t rb = route_groups(g.n_levels) * ((M + RT_BLOCK * SC_ROUTE_UNR - 1) / (RT_BLOCK * SC_ROUTE_UNR));
-    if (layout == MIPSF_FEAT_AOS)
-        hipLaunchKernelGGL(scatter_route_kernel<MIPSF_FEAT_AOS>, dim3(rb), dim3(RT_BLOCK), 0, s, x, dout, M, g, plan, ws, cw);
-    else
-        hipLaunchKernelGGL(scatter_route_kernel<MIPSF_FEAT_LEVEL_MAJOR>, dim3(rb), dim3(RT_BLOCK), 0, s, x, dout, M, g, plan, ws, cw);
-    return check_launch("hashgrid_route");
+    return with_layout(layout, [&](auto LAY) {
+        hipLaunchKernelGGL(scatter_route_kernel<LAY.value>, dim3(rb), dim3(RT_BLOCK), 0, s, x, dout, M, g, plan, ws, cw);
+        return check_launch("hashgrid_route");
+    });
 }
 
 // The routing half of the parameter-gradient scatter depends on the sample positions only: a caller may run it as soon
@@ -1855,43 +1855,20 @@ static int hashgrid_bwd_impl(const float* x, const float* params, const float* d
         per_cu = per_cu < 1u ? 1u : (per_cu > 2048u / SC_BLOCK ? 2048u / SC_BLOCK : per_cu);
         const uint32_t want = (uint32_t)cus * per_cu;
         const uint32_t blocks = plan.max_items < want ? plan.max_items : want;
-#define SCATTER(LAY)                                                                                             \
-    do {                                                                                                         \
-        static uint32_t attr_bytes_dev[MAX_DEVICES] = {0};                                                       \
-        uint32_t& attr_bytes = attr_bytes_dev[device_slot()];                                                    \
-        if (lds_bytes > attr_bytes) {                                                                            \
-            if (hipFuncSetAttribute((const void*)hashgrid_scatter_persist_kernel<LAY>,                           \
-                                    hipFuncAttributeMaxDynamicSharedMemorySize, lds_bytes) != hipSuccess) {      \
-                set_error("cannot raise dynamic LDS to %u bytes", lds_bytes);                                    \
-                return 4;                                                                                        \
-            }                                                                                                    \
-            attr_bytes = lds_bytes;                                                                              \
-        }                                                                                                        \
-        hipLaunchKernelGGL((hashgrid_scatter_persist_kernel<LAY>), dim3(blocks), dim3(SC_BLOCK), lds_bytes, s,   \
-                           x, dout, dparams, M, g, plan, ws, cw);                                                \
-    } while (0)
-        if (layout == MIPSF_FEAT_AOS) SCATTER(MIPSF_FEAT_AOS); else SCATTER(MIPSF_FEAT_LEVEL_MAJOR);
-#undef SCATTER
-        if (int e = check_launch("hashgrid_scatter")) return e;
+        const int rc = with_layout(layout, [&](auto LAY) {
+            constexpr auto kern = hashgrid_scatter_persist_kernel<LAY.value>;
+            if (!grant_lds<kern>(lds_bytes)) return lds_refused(lds_bytes);      // (the size grows with the largest slice)
+            hipLaunchKernelGGL(kern, dim3(blocks), dim3(SC_BLOCK), lds_bytes, s, x, dout, dparams, M, g, plan, ws, cw);
+            return check_launch("hashgrid_scatter");
+        });
+        if (rc) return rc;
         if (plan.fold_launch) {
             hipLaunchKernelGGL(hashgrid_scatter_reduce_kernel, dim3(plan.n_bins, (plan.max_slice + 255) / 256), dim3(256), 0, s,
                                dparams, g, plan, ws, cw);
             if (int e = check_launch("hashgrid_scatter_reduce")) return e;
         }
     }
-    if (dx) {
-        uint32_t nchunk;
-        const uint32_t nb = grid_blocks(M, g.n_levels, nchunk);
-        const float2* table = reinterpret_cast<const float2*>(params);
-        if (layout == MIPSF_FEAT_AOS)
-            hipLaunchKernelGGL(hashgrid_dx_kernel<MIPSF_FEAT_AOS>, dim3(nb), dim3(HG_BLOCK), 0, s, x, table, dout, dxl, M, g, nchunk);
-        else
-            hipLaunchKernelGGL(hashgrid_dx_kernel<MIPSF_FEAT_LEVEL_MAJOR>, dim3(nb), dim3(HG_BLOCK), 0, s, x, table, dout, dxl, M, g, nchunk);
-        if (int e = check_launch("hashgrid_dx")) return e;
-        const uint64_t n3 = (uint64_t)M * 3;
-        hipLaunchKernelGGL(hashgrid_dx_reduce_kernel, dim3((uint32_t)((n3 + 255) / 256)), dim3(256), 0, s, dxl, dx, n3, g.n_levels);
-        if (int e = check_launch("hashgrid_dx_reduce")) return e;
-    }
+    if (dx) return launch_dx(x, params, dout, dxl, dx, M, g, layout, s);
     return 0;
 }
 

@@ -7,6 +7,7 @@
 // helper_functions/utils.py:21-49, 71-111 (get_masks, get_sdf_loss).
 #include "pose_dev.h"
 #include "render_dev.h"
+#include "launch.h"
 #include <cstring>
 #include <cstddef>
 
@@ -915,27 +916,20 @@ static int launch_render_ticket(const mipsf_render_fwd_args* a, const RenderCfg&
                                 hipStream_t s) {
     const uint32_t N = a->N, S = a->S;
     const dim3 grid((N + RT_RPB - 1) / RT_RPB), block(RT_RPB * MIPSF_WAVE);
-    bool granted = S <= RT_MAX_S;
-    if (granted) {
+    if (S <= RT_MAX_S) {
         const uint32_t lds = (uint32_t)RT_RPB * S * 40u;
-        const int two = S > MIPSF_WAVE ? 1 : 0;       // samples per lane - 1
-        static uint32_t attr_dev[MAX_DEVICES][2] = {};
-        uint32_t& attr = attr_dev[device_slot()][a->draw ? 1 : 0];
-        if (lds > 48u * 1024u && lds > attr) {        // (only the two-samples-per-lane kernels get there)
-            const void* fn = a->draw ? (const void*)render_train_kernel<true, 2> : (const void*)render_train_kernel<false, 2>;
-            granted = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) == hipSuccess;
-            if (granted) attr = lds;       // (two threads racing here both set the attribute to a size that covers their launch: benign)
-            else (void)hipGetLastError();
-        }
-        if (granted) {
-#define RT_LAUNCH(D, K)                                                                                                              \
-    hipLaunchKernelGGL((render_train_kernel<D, K>), grid, block, lds, s, a->raw, a->z_vals, a->target_rgb, a->target_d, rc, a->rgb, \
-                       a->depth, a->depth_var, a->disp, a->acc, a->weights, a->partial, N, S, fin, a->draw)
-            if (a->draw) { if (two) RT_LAUNCH(true, 2); else RT_LAUNCH(true, 1); }
-            else { if (two) RT_LAUNCH(false, 2); else RT_LAUNCH(false, 1); }
-#undef RT_LAUNCH
+        // DRAW x samples per lane; only the two-samples-per-lane kernels pass the 48 KB every kernel may have unasked
+        const int e = with_bool(a->draw != nullptr, [&](auto DRAW) { return with_bool(S > MIPSF_WAVE, [&](auto TWO) {
+            constexpr auto kern = render_train_kernel<DRAW.value, TWO.value ? 2 : 1>;
+            if (TWO.value && lds > 48u * 1024u && !grant_lds<kern>(lds)) {
+                (void)hipGetLastError();
+                return -1;
+            }
+            hipLaunchKernelGGL(kern, grid, block, lds, s, a->raw, a->z_vals, a->target_rgb, a->target_d, rc, a->rgb, a->depth,
+                               a->depth_var, a->disp, a->acc, a->weights, a->partial, N, S, fin, a->draw);
             return check_launch(what);
-        }
+        }); });
+        if (e >= 0) return e;       // (-1: not granted)
         MIPSF_REQUIRE(a->draw == nullptr, "draw: this device does not grant render_train_kernel's %u bytes of LDS", lds);
     }
     hipLaunchKernelGGL((render_fwd_kernel<true, true, RT_RPB>), grid, block, 0, s, a->raw, a->z_vals, a->target_rgb, a->target_d, rc,

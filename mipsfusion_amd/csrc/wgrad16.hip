@@ -46,6 +46,7 @@
 // (small rows = d logits (5) and d rgb (3) of `dsmall`: d w_sdf2, d w_rgb0).  Bias gradients are register sums of the
 // transposed tiles.  Per-block partial records + the reduce kernel of decoder.hip (no atomics on weights).
 #include "decoder_dev.h"
+#include "launch.h"
 
 namespace mipsf {
 using namespace dl;
@@ -1567,16 +1568,23 @@ extern "C" int mipsf_decoder_wgrad16(const mipsf_decoder_wgrad16_args* a, void* 
     uint32_t blocks = n_tiles < (uint32_t)cus ? n_tiles : (uint32_t)cus;
     if (blocks > (uint32_t)W16_MAX_BLOCKS) blocks = (uint32_t)W16_MAX_BLOCKS;
     const uint32_t* live = tile_live;
-#define W16(LAY, AR, RC, CP) hipLaunchKernelGGL((decoder_wgrad16_kernel<LAY, AR, RC, CP>), dim3(blocks), dim3(W16_BLOCK), 0, s, packed16, \
-                                                feat, x, saved, dact, dsmall, partial, M, n_tiles, live, lean_dact, live_list, (uint32_t)saved_bytes)
-    // a live-sample list: compact mode; packed16: the lean record (both the transpose-read form); else the streaming form
-#define W16_L(LAY) do { if (live_list) { if (arithmetic == MIPSF_PREC_F16X3) W16(LAY, ArF16, true, true); else W16(LAY, ArBF3, true, true); } \
-                        else if (arithmetic == MIPSF_PREC_F16X3) { if (packed16) W16(LAY, ArF16, true, false); else W16(LAY, ArF16, false, false); } \
-                        else if (arithmetic == MIPSF_PREC_BF16X6) { if (packed16) W16(LAY, ArBF3, true, false); else W16(LAY, ArBF3, false, false); } \
-                        else W16(LAY, ArBF2, false, false); } while (0)
-    if (feat_layout == MIPSF_FEAT_AOS) W16_L(MIPSF_FEAT_AOS); else W16_L(MIPSF_FEAT_LEVEL_MAJOR);
-#undef W16_L
-#undef W16
-    if (int e = check_launch("decoder_wgrad16")) return e;
+    const int rc = with_layout(feat_layout, [&](auto LAY) {
+        auto arm = [&](auto AR, auto RECOMP, auto CP) {
+            hipLaunchKernelGGL((decoder_wgrad16_kernel<LAY.value, decltype(AR), RECOMP.value, CP.value>), dim3(blocks), dim3(W16_BLOCK), 0,
+                               s, packed16, feat, x, saved, dact, dsmall, partial, M, n_tiles, live, lean_dact, live_list,
+                               (uint32_t)saved_bytes);
+            return check_launch("decoder_wgrad16");
+        };
+        // (arithmetic, H1 recomputed, compact tiles).  A live-sample list: compact mode; packed16: the lean record (both the
+        // transpose-read form); else the streaming form, the only one of bf16x3
+        constexpr ArF16 f16;
+        constexpr ArBF3 bf3;
+        constexpr ArBF2 bf2;
+        if (live_list) return arithmetic == MIPSF_PREC_F16X3 ? arm(f16, yes, yes) : arm(bf3, yes, yes);
+        if (arithmetic == MIPSF_PREC_F16X3) return packed16 ? arm(f16, yes, no) : arm(f16, no, no);
+        if (arithmetic == MIPSF_PREC_BF16X6) return packed16 ? arm(bf3, yes, no) : arm(bf3, no, no);
+        return arm(bf2, no, no);
+    });
+    if (rc) return rc;
     return wgrad_reduce_launch(partial, blocks, grads, s, det);
 }

@@ -44,6 +44,12 @@ def assert_close(a, b, tol, what=""):
     assert e <= tol, f"{what}: max error relative to max magnitude {e:.3e} > {tol:.1e}"
 
 
+def persistent_m(M):
+    """The parameter value "persistent": the smallest batch at which the decoder's persistent (*_lds_kernel) forms are taken
+    -- 16 wave tiles of 32 samples for every CU of this device -- plus one full tile and a ragged one."""
+    return _lib.lib().mipsf_device_cu_count() * 16 * 32 + 33 if M == "persistent" else M
+
+
 def assert_grad_close(a, b, tol, what="", outlier_frac=1e-4):
     """Gradients pass through ReLU / first-crossing / band masks: two fp32 implementations with different summation
     orders legitimately flip O(1) of millions of such decisions, which moves a handful of entries.  Require the
@@ -1472,10 +1478,13 @@ def test_sdf_only_forward_is_column_3_bit_for_bit(dev):
     packed = ops.decoder_pack(m.decoder.ordered_parameters())
     for M in (1, 33, 1000, 70001, 300000):
         xn = torch.rand(M, 3, device=dev)
-        feat = ops.hashgrid_fwd(xn, m.embed_fn.params.detach(), m.embed_fn.meta, ops.FEAT_LEVEL_MAJOR)
-        full, _ = ops.decoder_fwd(packed, feat, ops.FEAT_LEVEL_MAJOR, xn, None, M, save=False)
-        sdf = ops.decoder_fwd_sdf(packed, feat, ops.FEAT_LEVEL_MAJOR, xn, None, M)
-        assert torch.equal(sdf, full[:, 3]), M
+        # both feature layouts; the positional encoding computed in the kernel (None) or handed in (pe_mode 1)
+        for lay in (ops.FEAT_LEVEL_MAJOR, ops.FEAT_AOS):
+            feat = ops.hashgrid_fwd(xn, m.embed_fn.params.detach(), m.embed_fn.meta, lay)
+            for pe in (None, torch.rand(M, 48, device=dev) * 2 - 1):
+                full, _ = ops.decoder_fwd(packed, feat, lay, xn, pe, M, save=False)
+                sdf = ops.decoder_fwd_sdf(packed, feat, lay, xn, pe, M)
+                assert torch.equal(sdf, full[:, 3]), (M, lay, pe is not None)
     pts = torch.rand(5000, 3, device=dev) * 2 - 1
     with torch.no_grad():
         assert torch.equal(m.query_sdf(pts), m.query_color_sdf(pts)[..., 3:4])
@@ -1734,12 +1743,13 @@ def test_fused_adam_capturable_state_dict_roundtrip(dev):
 
 
 # ------------------------------------------------------------------ f16-MFMA decoder forward (csrc/decoder16.hip)
-@pytest.mark.parametrize("M", [1, 33, 1000, 70000])
+@pytest.mark.parametrize("M", [1, 33, 1000, 70000, "persistent"])
 @pytest.mark.parametrize("layout", ["aos", "level_major"])
 def test_decoder_f16x3_forward_matches_fp32_kernel_and_oracle(dev, M, layout):
     """precision "f16x3" (hi/lo split operands on v_mfma_f32_32x32x16_f16) vs the fp32-MFMA kernel and the oracle:
     outputs to fp32 round-off class, the saved-activation record element for element (same layout: the fp32 backward
-    kernels consume it unchanged).  Small-batch and persistent (M = 70000) variants, both feature layouts."""
+    kernels consume it unchanged).  Small-batch and persistent (M = "persistent") variants, both feature layouts."""
+    M = persistent_m(M)
     torch.manual_seed(M)
     dec = MLP_reg({}, input_ch=32, input_ch_pos=48).to(dev)
     with torch.no_grad():
@@ -1764,6 +1774,8 @@ def test_decoder_f16x3_forward_matches_fp32_kernel_and_oracle(dev, M, layout):
     assert_close(o16, ref, 3e-6, "f16x3 vs oracle")
     sdf16 = ops.decoder_fwd_sdf(packed, feat, lay, x, None, M, precision="f16x3", packed16=packed16)
     assert torch.equal(sdf16, o16[:, 3]), "f16x3 SDF-only branch = column 3 of the full f16x3 forward, bit for bit"
+    o16n, none = ops.decoder_fwd(packed, feat, lay, x, None, M, save=False, precision="f16x3", packed16=packed16)
+    assert none is None and torch.equal(o16n, o16), "save=False: same outputs"
     # plain f16 operands: forward-only, stated tolerance 2e-3 of the output range
     p16, none = ops.decoder_fwd(packed, feat, lay, x, None, M, save=False, precision="f16", packed16=packed16)
     assert none is None
@@ -1773,7 +1785,7 @@ def test_decoder_f16x3_forward_matches_fp32_kernel_and_oracle(dev, M, layout):
     assert float((sdfp - p16[:, 3]).abs().max()) <= 1e-6, "SDF-only branch = column 3 of the full plain-f16 forward"
 
 
-@pytest.mark.parametrize("M", [64, 4096 + 17, 70000])
+@pytest.mark.parametrize("M", [64, 4096 + 17, 70000, "persistent"])
 @pytest.mark.parametrize("layout", ["aos", "level_major"])
 def test_decoder_backward_short_cuts_zero_gradient_tiles_exactly(dev, M, layout):
     """ops.decoder_bwd with the zero-tile flags (mipsf_decoder_bwd_chain16 + mipsf_decoder_wgrad16) against the
@@ -1782,6 +1794,7 @@ def test_decoder_backward_short_cuts_zero_gradient_tiles_exactly(dev, M, layout)
     be EQUAL (the skipped tiles are zeros either way, the others go through the same arithmetic); the parameter gradients
     agree to fp32 class (the tiles are dealt to the weight-gradient workgroups in a different order); a frozen decoder
     (no weight gradients) takes the short cut too; a batch without any gradient gives zeros."""
+    M = persistent_m(M)
     torch.manual_seed(7 + M)
     dec = MLP_reg({}, input_ch=32, input_ch_pos=48).to(dev)
     ws = dec.ordered_parameters()
@@ -1916,15 +1929,17 @@ def test_decoder_f16x3_backward_chain_matches_fp32_kernel(dev, M, layout):
         assert_close(a, b, 3e-6, "stream_f16x3 behind the fp32 chain, grad " + k)
     # opt-in: the three large weight-gradient products on the bf16 matrix cores with hi/lo split operands (16-17 bits
     # per operand, fp32 accumulate): per-term error 2^-16, zero-mean, averaged over the batch -> ~5e-6 of the maximum
-    gbf = [torch.zeros_like(w) for w in ws]
-    ops.decoder_bwd(None, feat, lay, x, None, out, dout, saved, gbf, M, precision="f16x3", packed16=packed16,
-                    wgrad_precision="bf16x3")
-    for k, a, b in zip(ops.DECODER_PARAM_ORDER, gbf, g32):
-        assert_close(a, b, 2e-5, "bf16x3 grad " + k)
+    # (the LDS kernel, and the streaming kernel on two bf16 planes: the same operands, the same bound)
+    for wp in ("bf16x3", "stream_bf16x3"):
+        gbf = [torch.zeros_like(w) for w in ws]
+        ops.decoder_bwd(None, feat, lay, x, None, out, dout, saved, gbf, M, precision="f16x3", packed16=packed16,
+                        wgrad_precision=wp)
+        for k, a, b in zip(ops.DECODER_PARAM_ORDER, gbf, g32):
+            assert_close(a, b, 2e-5, wp + " grad " + k)
 
 
 # ------------------------------------------------------------------ bf16x6: fp32 operands as three bf16 pieces, six products
-@pytest.mark.parametrize("M", [1, 33, 1000, 70000])
+@pytest.mark.parametrize("M", [1, 33, 1000, 70000, "persistent"])
 @pytest.mark.parametrize("layout", ["aos", "level_major"])
 def test_decoder_bf16x6_matches_fp32_kernel_and_oracle(dev, M, layout):
     """precision "bf16x6" (csrc/decoder16.hip, NP = 3: every operand carried exactly as p0 + p1 + p2 in bf16, a product =
@@ -1932,7 +1947,8 @@ def test_decoder_bf16x6_matches_fp32_kernel_and_oracle(dev, M, layout):
     oracle -- the arithmetic of model/decoder.py:32-50's fp32 nn.Linear layers.  Forward: outputs, the saved record element
     for element, the SDF-only branch bit for bit; every record form (full, lean, masks) gives the same outputs.  Backward:
     the chain on the SAME record as the fp32 chain (d features, d x), the streaming weight-gradient kernel on three bf16
-    planes behind it, the zero-tile short cut, a frozen decoder.  Small-batch and persistent (M = 70000) kernels."""
+    planes behind it, the zero-tile short cut, a frozen decoder.  Small-batch and persistent (M = "persistent") kernels."""
+    M = persistent_m(M)
     torch.manual_seed(300 + M)
     dec = MLP_reg({}, input_ch=32, input_ch_pos=48).to(dev)
     with torch.no_grad():
