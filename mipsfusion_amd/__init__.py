@@ -19,6 +19,7 @@ _MESH_RENDER = ("render_mesh_depth", "depth_l1", "visible_points", "DepthMetrics
                 "MeshRender", "MeshRenderMetrics")
 _TSDF = ("TSDFVolume", "TSDFCounts", "tsdf_mesh_from_frames", "mesh_from_rendered_depth", "Raycast", "TrackResult", "tsdf_odometry",
          "ColorTrackResult")
+_SPARSE_TSDF = ("SparseTSDFVolume", "SparseTSDFCounts", "sparse_tsdf_mesh_from_frames", "sparse_tsdf_odometry")
 # (the function image_metrics.image_metrics is reached through its module: the package attribute of that name IS the module)
 _IMAGE_METRICS = ("psnr", "ssim", "ms_ssim", "render_metrics", "gaussian_window", "ImageMetrics", "RenderMetrics")
 _TRAJECTORY = ("align_trajectory", "trajectory_metrics", "TrajectoryMetrics")
@@ -50,6 +51,9 @@ def __getattr__(name):
     if name in _TSDF:                       # depth frames fused into a TSDF volume and meshed (mipsfusion_amd/tsdf.py), the same way
         from . import tsdf
         return getattr(tsdf, name)
+    if name in _SPARSE_TSDF:                # the same volume kept only near surfaces, past 2^31 voxels (mipsfusion_amd/sparse_tsdf.py)
+        from . import sparse_tsdf
+        return getattr(sparse_tsdf, name)
     if name in _IMAGE_METRICS:              # rendered frames against captured ones: PSNR, SSIM, MS-SSIM (mipsfusion_amd/image_metrics.py)
         from . import image_metrics
         return getattr(image_metrics, name)

@@ -412,6 +412,42 @@ TRACK_COLOR_SIGNATURES = {
 }
 
 
+# include/mipsf_sparse.h (the TSDF volume kept only where a depth pixel put a surface: an index grid of bricks and a pool of slots)
+SPARSE_BRICK_VOXELS, SPARSE_MAX_BRICKS, SPARSE_MAX_CAPACITY, SPARSE_MAX_STEPS, SPARSE_MAX_VIEWS = 1024, 0x7FFFFFFF, 0x100000, 4096, 65535
+SPARSE_SCAN_TILE = 1024
+SPARSE_NO_SKIP = 1
+SPARSE_ALLOC_RECORD_WORDS = 4              # uint64 marked, created, dropped, in_use
+
+
+class SparseVolume(C.Structure):
+    _fields_ = [("X", _CU), ("Y", _CU), ("Z", _CU), ("capacity", _CU), ("origin", C.c_double * 3), ("voxel", C.c_double), ("ticks", _VP * 3),
+                ("table", _VP), ("slot_brick", _VP), ("birth", _VP), ("count", _VP), ("tsdf", _VP), ("weight", _VP), ("color", _VP)]
+
+
+SparseAllocateArgs = _args("SparseAllocateArgs", [("n", _CU), ("H", _CU), ("W", _CU), ("steps", _CU), ("reserved", _CU),
+                                                  ("fx", C.c_double), ("fy", C.c_double), ("cx", C.c_double), ("cy", C.c_double),
+                                                  ("depth_max", C.c_double), ("band", C.c_double), ("vol", SparseVolume), ("depth", _VP),
+                                                  ("poses", _VP), ("mark", _VP), ("scan", _VP), ("record", _VP)])
+SparseIntegrateArgs = _args("SparseIntegrateArgs", [("n", _CU), ("H", _CU), ("W", _CU), ("flags", _CU), ("reserved", _CU),
+                                                    ("fx", C.c_double), ("fy", C.c_double), ("cx", C.c_double), ("cy", C.c_double),
+                                                    ("trunc", C.c_double), ("depth_max", C.c_double), ("max_weight", C.c_double),
+                                                    ("vol", SparseVolume), ("depth", _VP), ("rgb", _VP), ("poses", _VP), ("record", _VP)])
+SparseGatherArgs = _args("SparseGatherArgs", [("lo", _CU * 3), ("hi", _CU * 3), ("reserved", _CU), ("vol", SparseVolume), ("tsdf", _VP),
+                                              ("weight", _VP), ("color", _VP)])
+SparseRaycastArgs = _args("SparseRaycastArgs", [("n", _CU), ("H", _CU), ("W", _CU), ("flags", _CU), ("reserved", _CU), ("trunc", C.c_double),
+                                                ("fx", C.c_double), ("fy", C.c_double), ("cx", C.c_double), ("cy", C.c_double),
+                                                ("near", C.c_double), ("far", C.c_double), ("step", C.c_double), ("min_weight", C.c_double),
+                                                ("vol", SparseVolume), ("poses", _VP), ("depth", _VP), ("normals", _VP), ("color_out", _VP),
+                                                ("record", _VP)])
+SPARSE_SIGNATURES = {
+    "mipsf_sparse_scan_words": (_U64, [_U32, _U32, _U32]),
+    "mipsf_sparse_allocate": (_I, [C.POINTER(SparseAllocateArgs), _P]),
+    "mipsf_sparse_integrate": (_I, [C.POINTER(SparseIntegrateArgs), _P]),
+    "mipsf_sparse_gather": (_I, [C.POINTER(SparseGatherArgs), _P]),
+    "mipsf_sparse_raycast": (_I, [C.POINTER(SparseRaycastArgs), _P]),
+}
+
+
 # include/mipsf_image.h (two image stacks compared: error sums, valid-region SSIM and its cs term, the MS-SSIM pyramid's 2 x 2 mean)
 IMAGE_F32, IMAGE_F64 = 0, 1
 IMAGE_WINDOW, IMAGE_TILE_H, IMAGE_TILE_W, IMAGE_MAX_CHANNELS, IMAGE_MAX_SIDE = 11, 16, 32, 4, 8192
@@ -498,7 +534,7 @@ def lib() -> C.CDLL:
                                        + list(SUBMAP_SIGNATURES.items()) + list(EVAL_SIGNATURES.items())
                                        + list(RASTER_SIGNATURES.items()) + list(TSDF_SIGNATURES.items())
                                        + list(IMAGE_SIGNATURES.items()) + list(TRACK_SIGNATURES.items()) + list(TRACK_COLOR_SIGNATURES.items())
-                                       + list(SHADE_SIGNATURES.items())):
+                                       + list(SHADE_SIGNATURES.items()) + list(SPARSE_SIGNATURES.items())):
             fn = getattr(handle, name)
             fn.restype = res
             fn.argtypes = args

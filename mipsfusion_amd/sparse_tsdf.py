@@ -1,0 +1,342 @@
+"""The TSDF volume of ``tsdf.py`` kept only where a depth pixel put a surface: a virtual grid of bricks of 8 x 8 x 16 voxels that may
+hold 2^31 voxels and more, an index grid with one word per brick, and a pool of ``capacity_bricks`` brick-sized slots.  A brick gets
+a slot when a depth pixel of a fused view lands within ``band`` of it; only allocated bricks are fused, ray cast and gathered.  The
+kernels are those of ``csrc/sparse.hip`` (C ABI: include/mipsf_sparse.h):
+
+    SparseTSDFVolume               the state (index grid, pool of tsdf, weight, optionally colour; all on the device) and integrate /
+                                   to_dense / extract_mesh / raycast / track / reset
+    sparse_tsdf_mesh_from_frames   depth frames + poses -> mesh.Mesh, the namesake of tsdf_mesh_from_frames
+    sparse_tsdf_odometry           depth frames -> poses, the namesake of tsdf_odometry
+
+Every output is the dense volume's rule read over the dense state with the voxels of unallocated bricks left at zero, and EQUALS the
+float64 restatement in tests/sparse_cpu.py.  Meshing goes through ``to_dense``: a window of the grid as a TSDFVolume, so a window of
+2^31 voxels is still the limit of one marching call.  Nothing is ever freed.  There is no CPU fallback.
+"""
+from __future__ import annotations
+
+import ctypes as C
+import math
+from typing import NamedTuple, Optional
+
+import numpy as np
+import torch
+
+from . import _lib
+from .mesh import Mesh
+from .mesh_render import _poses
+from .scene_mesh import _intrinsics
+from .tsdf import Raycast, TSDFVolume, _device, _images, frames_bounds
+
+BRICK = _lib.TSDF_BRICK
+
+
+class SparseTSDFCounts(NamedTuple):
+    updates: int                     # (voxel, view) pairs that updated, over the calls of one integrate()
+    observed: int                    # voxels whose weight is positive afterwards
+    marked: int                      # bricks the views marked, summed over the calls
+    new: int                         # bricks that got a slot
+    dropped: int                     # bricks that wanted a slot when the pool was full, summed over the calls
+    bricks_in_use: int               # slots in use afterwards
+
+
+class SparseTSDFVolume:
+    """A brick-sparse TSDF volume on the device.  Voxel (i,j,k) of the virtual grid ``dims`` sits at origin + voxel_size * (i,j,k);
+    ``trunc``, ``max_weight`` and the words are those of TSDFVolume.  ``capacity_bricks`` slots of 1024 voxels are allocated at once
+    (8 KB a slot, 20 KB with colour); ``band`` (trunc by default) is how far in front of and behind a depth pixel bricks are
+    allocated."""
+
+    def __init__(self, origin, voxel_size: float, dims, trunc: float, capacity_bricks: int, color: bool = False, max_weight: float = math.inf,
+                 band: Optional[float] = None, device=None):
+        self.origin = np.asarray(origin, np.float64).reshape(3).copy()
+        self.voxel_size, self.trunc, self.max_weight = float(voxel_size), float(trunc), float(max_weight)
+        self.band = self.trunc if band is None else float(band)
+        self.dims = tuple(int(d) for d in dims)
+        self.capacity = int(capacity_bricks)
+        if len(self.dims) != 3 or min(self.dims) < 1 or max(self.dims) >= 1 << 32:
+            raise ValueError(f"dims: expected three positive counts, got {dims}")
+        if not (self.voxel_size > 0 and math.isfinite(self.voxel_size)):
+            raise ValueError(f"voxel_size {voxel_size} is not positive and finite")
+        if not (self.band >= 0 and math.isfinite(self.band)):
+            raise ValueError(f"band {band} is negative, infinite or not a number")
+        self.bricks = tuple(-(-d // b) for d, b in zip(self.dims, BRICK))
+        if self.bricks[0] * self.bricks[1] * self.bricks[2] > _lib.SPARSE_MAX_BRICKS:
+            raise ValueError(f"a grid of {self.dims[0]} x {self.dims[1]} x {self.dims[2]} voxels has 2^31 bricks or more; choose a larger "
+                             f"voxel size or smaller bounds")
+        if not 1 <= self.capacity <= _lib.SPARSE_MAX_CAPACITY:
+            raise ValueError(f"capacity_bricks {capacity_bricks}: from 1 to {_lib.SPARSE_MAX_CAPACITY}")
+        self.steps = int(math.ceil(self.band / self.voxel_size))
+        self.device = _device(device)
+        self.ticks = tuple(self.origin[a] + self.voxel_size * np.arange(self.dims[a], dtype=np.float64) for a in range(3))
+        lib = _lib.lib()
+        with torch.cuda.device(self.device):
+            dev = self.device
+            self._ticks_dev = tuple(torch.from_numpy(t).to(dev) for t in self.ticks)
+            self.table = torch.full(self.bricks, -1, dtype=torch.int32, device=dev)
+            self.slot_brick = torch.zeros(self.capacity, dtype=torch.int32, device=dev)
+            self.count = torch.zeros(1, dtype=torch.int32, device=dev)
+            self.tsdf = torch.zeros((self.capacity,) + BRICK, dtype=torch.float32, device=dev)
+            self.weight = torch.zeros((self.capacity,) + BRICK, dtype=torch.float32, device=dev)
+            self.color = torch.zeros((self.capacity,) + BRICK + (3,), dtype=torch.float32, device=dev) if color else None
+            self._birth = torch.zeros(self.capacity, dtype=torch.int32, device=dev)
+            self._mark = torch.empty(self.bricks, dtype=torch.int32, device=dev)
+            self._scan = torch.empty(int(lib.mipsf_sparse_scan_words(*self.dims)), dtype=torch.int32, device=dev)
+        self._bind()
+
+    def _bind(self) -> None:
+        """the volume as the C ABI takes it (mipsf_sparse_volume), from the tensors as they are now"""
+        g = _lib.SparseVolume()
+        g.X, g.Y, g.Z, g.capacity, g.voxel = self.dims[0], self.dims[1], self.dims[2], self.capacity, self.voxel_size
+        with torch.cuda.device(self.device):
+            for d in range(3):
+                g.origin[d] = float(self.origin[d])
+                g.ticks[d] = _lib.dptr(self._ticks_dev[d], torch.float64)
+            g.table, g.slot_brick = _lib.dptr(self.table, torch.int32), _lib.dptr(self.slot_brick, torch.int32)
+            g.birth, g.count = _lib.dptr(self._birth, torch.int32), _lib.dptr(self.count, torch.int32)
+            g.tsdf, g.weight, g.color = _lib.dptr(self.tsdf), _lib.dptr(self.weight), _lib.dptr(self.color)
+        self._vol = g
+
+    def reset(self) -> None:
+        self.table.fill_(-1)
+        self.count.zero_()
+        for t in (self.tsdf, self.weight, self.color):
+            if t is not None:
+                t.zero_()
+
+    # ----------------------------------------------------------------------------------------------------------- enqueue only
+    def _views(self, depth, poses, rgb):
+        _lib.dptr(depth), _lib.dptr(poses), _lib.dptr(rgb)
+        if depth.dim() != 3 or tuple(poses.shape) != (depth.shape[0], 4, 4):
+            raise ValueError(f"expected depth [n,H,W] and poses [n,4,4], got {tuple(depth.shape)} and {tuple(poses.shape)}")
+        if rgb is not None and tuple(rgb.shape) != tuple(depth.shape) + (3,):
+            raise ValueError(f"rgb: expected {tuple(depth.shape) + (3,)}, got {tuple(rgb.shape)}")
+        if (rgb is None) != (self.color is None):
+            raise ValueError("rgb goes with a volume made with color=True, and such a volume needs rgb")
+
+    def allocate_enqueue(self, depth: torch.Tensor, poses: torch.Tensor, K, depth_max: float = math.inf,
+                         record: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """mipsf_sparse_allocate; nothing is read back -> record int64 [4] on the device: bricks marked, new, dropped, in use"""
+        _lib.dptr(depth), _lib.dptr(poses)
+        fx, fy, cx, cy = (float(x) for x in _intrinsics(K))
+        n, H, W = depth.shape
+        with torch.cuda.device(self.device):
+            record = torch.empty(_lib.SPARSE_ALLOC_RECORD_WORDS, dtype=torch.int64, device=self.device) if record is None else record
+            a = _lib.SparseAllocateArgs.new(n=n, H=H, W=W, steps=self.steps, fx=fx, fy=fy, cx=cx, cy=cy, depth_max=float(depth_max), band=self.band,
+                                            vol=self._vol, depth=depth.data_ptr() if n else None, poses=poses.data_ptr() if n else None,
+                                            mark=self._mark.data_ptr(), scan=self._scan.data_ptr(), record=_lib.dptr(record, torch.int64))
+            _lib.check(_lib.lib().mipsf_sparse_allocate(C.byref(a), _lib.stream_ptr()), "sparse_allocate")
+        return record
+
+    def fuse_enqueue(self, depth: torch.Tensor, poses: torch.Tensor, K, rgb: Optional[torch.Tensor] = None, depth_max: float = math.inf,
+                     record: Optional[torch.Tensor] = None, flags: int = 0) -> torch.Tensor:
+        """mipsf_sparse_integrate over the slots in use, with the births the last allocate_enqueue left; nothing is read back
+        -> record int64 [2] on the device"""
+        self._views(depth, poses, rgb)
+        fx, fy, cx, cy = (float(x) for x in _intrinsics(K))
+        n, H, W = depth.shape
+        with torch.cuda.device(self.device):
+            record = torch.empty(_lib.TSDF_RECORD_WORDS, dtype=torch.int64, device=self.device) if record is None else record
+            a = _lib.SparseIntegrateArgs.new(n=n, H=H, W=W, flags=int(flags), fx=fx, fy=fy, cx=cx, cy=cy, trunc=self.trunc,
+                                             depth_max=float(depth_max), max_weight=self.max_weight, vol=self._vol,
+                                             depth=depth.data_ptr() if n else None, rgb=None if rgb is None or not n else rgb.data_ptr(),
+                                             poses=poses.data_ptr() if n else None, record=_lib.dptr(record, torch.int64))
+            _lib.check(_lib.lib().mipsf_sparse_integrate(C.byref(a), _lib.stream_ptr()), "sparse_integrate")
+        return record
+
+    def integrate_enqueue(self, depth: torch.Tensor, poses: torch.Tensor, K, rgb: Optional[torch.Tensor] = None,
+                          depth_max: float = math.inf, flags: int = 0):
+        """Allocates for the views, then fuses them; nothing is read back.  depth fp32 [n,H,W], poses fp32 [n,4,4], rgb fp32
+        [n,H,W,3] or None, all on the device -> (record int64 [2]: pairs updated, voxels observed; record int64 [4]: bricks marked,
+        new, dropped, in use), both on the device"""
+        self._views(depth, poses, rgb)
+        alloc = self.allocate_enqueue(depth, poses, K, depth_max)
+        return self.fuse_enqueue(depth, poses, K, rgb, depth_max, flags=flags), alloc
+
+    def gather_enqueue(self, lo, hi) -> TSDFVolume:
+        """mipsf_sparse_gather: the window lo <= index < hi as a TSDFVolume; nothing is read back"""
+        lo, hi = tuple(int(x) for x in lo), tuple(int(x) for x in hi)
+        if len(lo) != 3 or len(hi) != 3 or any(not 0 <= a < b <= d for a, b, d in zip(lo, hi, self.dims)):
+            raise ValueError(f"window {lo} .. {hi} of a grid of {self.dims}")
+        n = tuple(b - a for a, b in zip(lo, hi))
+        if n[0] * n[1] * n[2] > _lib.TSDF_MAX_VOXELS:
+            raise ValueError(f"a window of {n[0]} x {n[1]} x {n[2]} voxels has 2^31 voxels or more; take it in parts (to_dense(lo, hi))")
+        out = TSDFVolume(self.origin + self.voxel_size * np.asarray(lo, np.float64), self.voxel_size, n, self.trunc, self.color is not None,
+                         self.max_weight, self.device)
+        # the window's voxels keep the positions they have in the virtual grid, to the last bit
+        out.ticks = tuple(self.ticks[d][lo[d]:hi[d]] for d in range(3))
+        out._ticks_dev = tuple(self._ticks_dev[d][lo[d]:hi[d]] for d in range(3))
+        with torch.cuda.device(self.device):
+            a = _lib.SparseGatherArgs.new(vol=self._vol, tsdf=_lib.dptr(out.tsdf), weight=_lib.dptr(out.weight), color=_lib.dptr(out.color))
+            for d in range(3):
+                a.lo[d], a.hi[d] = lo[d], hi[d]
+            _lib.check(_lib.lib().mipsf_sparse_gather(C.byref(a), _lib.stream_ptr()), "sparse_gather")
+        return out
+
+    def raycast_enqueue(self, poses: torch.Tensor, K, H: int, W: int, near: float = 0.0, far: float = math.inf, step: Optional[float] = None,
+                        min_weight: float = 1.0, normals: bool = True, color: bool = False, flags: int = 0) -> Raycast:
+        """mipsf_sparse_raycast; nothing is read back.  poses fp32 [n,4,4] on the device -> Raycast of device tensors"""
+        _lib.dptr(poses)
+        if poses.dim() != 3 or tuple(poses.shape[1:]) != (4, 4):
+            raise ValueError(f"poses: expected [n,4,4], got {tuple(poses.shape)}")
+        if color and self.color is None:
+            raise ValueError("the volume was made without colour")
+        fx, fy, cx, cy = (float(x) for x in _intrinsics(K))
+        n, H, W = poses.shape[0], int(H), int(W)
+        with torch.cuda.device(self.device):
+            depth = torch.empty(n, H, W, dtype=torch.float32, device=self.device)
+            nrm = torch.empty(n, H, W, 3, dtype=torch.float32, device=self.device) if normals else None
+            col = torch.empty(n, H, W, 3, dtype=torch.float32, device=self.device) if color else None
+            record = torch.empty(_lib.TRACK_RECORD_WORDS, dtype=torch.int64, device=self.device)
+            a = _lib.SparseRaycastArgs.new(n=n, H=H, W=W, flags=int(flags), trunc=self.trunc, fx=fx, fy=fy, cx=cx, cy=cy, near=float(near),
+                                           far=float(far), step=0.5 * self.trunc if step is None else float(step), min_weight=float(min_weight),
+                                           vol=self._vol, poses=poses.data_ptr() if n else None, depth=depth.data_ptr() if n else None,
+                                           normals=nrm.data_ptr() if normals and n else None,
+                                           color_out=col.data_ptr() if color and n else None, record=_lib.dptr(record, torch.int64))
+            _lib.check(_lib.lib().mipsf_sparse_raycast(C.byref(a), _lib.stream_ptr()), "sparse_raycast")
+        return Raycast(depth, nrm, col, record)
+
+    # the registration takes any ray-cast images: TSDFVolume's two methods run as they are, on this volume's raycast_enqueue
+    track_enqueue = TSDFVolume.track_enqueue
+    track = TSDFVolume.track
+
+    # ----------------------------------------------------------------------------------------------------------- public
+    def integrate(self, depth, c2w, K, rgb=None, depth_max: float = math.inf, views_per_call: Optional[int] = None) -> SparseTSDFCounts:
+        """Allocates bricks for the views and fuses them in the order given; the arguments are those of TSDFVolume.integrate.  The
+        views are cut into calls of ``views_per_call`` (all in one by default, at most 65535); while nothing is dropped the cut does
+        not reach the bytes of any brick, only the numbering of the slots.  One read-back of 48 bytes per call."""
+        with torch.cuda.device(self.device):
+            D = _images(depth, self.device, 0, "depth")
+            P = _poses(c2w, self.device)
+            C3 = None if rgb is None else _images(rgb, self.device, 3, "rgb")
+            n = D.shape[0]
+            if P.shape[0] != n:
+                raise ValueError(f"{n} depth images and {P.shape[0]} poses")
+            per = min(max(n, 1), _lib.SPARSE_MAX_VIEWS) if views_per_call is None else int(views_per_call)
+            if per < 1:
+                raise ValueError("views_per_call must be positive")
+            records = [torch.cat(self.integrate_enqueue(D[k:k + per], P[k:k + per], K, None if C3 is None else C3[k:k + per], depth_max))
+                       for k in range(0, max(n, 1), per)]
+            got = torch.stack(records).cpu().numpy()
+        return SparseTSDFCounts(int(got[:, 0].sum()), int(got[-1, 1]), int(got[:, 2].sum()), int(got[:, 3].sum()), int(got[:, 4].sum()),
+                                int(got[-1, 5]))
+
+    def allocated_bricks(self) -> np.ndarray:
+        """the bricks in use, in slot order -> int64 [m,3] brick coordinates (one read-back of slot_brick)"""
+        got = torch.cat([self.count, self.slot_brick]).cpu().numpy().astype(np.int64)
+        b = got[1:1 + min(int(got[0]), self.capacity)]
+        return np.stack([b // (self.bricks[1] * self.bricks[2]), (b // self.bricks[2]) % self.bricks[1], b % self.bricks[2]], 1)
+
+    def tight_window(self):
+        """-> (lo, hi): the box of the allocated bricks in voxel indices, hi exclusive; None when nothing is allocated"""
+        b = self.allocated_bricks()
+        if len(b) == 0:
+            return None
+        size = np.asarray(BRICK, np.int64)
+        return tuple(int(x) for x in b.min(0) * size), tuple(int(x) for x in np.minimum((b.max(0) + 1) * size, np.asarray(self.dims, np.int64)))
+
+    def to_dense(self, lo=None, hi=None) -> TSDFVolume:
+        """The window lo <= voxel index < hi of the volume as a dense TSDFVolume, zeros where no brick is allocated; by default the
+        tight box of the allocated bricks.  Its voxels sit where they sit in this volume, so it can be marched, ray cast, tracked
+        against and fused into like any other.  Refused when the window holds 2^31 voxels or more."""
+        if lo is None or hi is None:
+            box = self.tight_window()
+            if box is None:
+                box = ((0, 0, 0), tuple(min(d, b) for d, b in zip(self.dims, BRICK)))
+            lo, hi = (box[0] if lo is None else lo), (box[1] if hi is None else hi)
+        return self.gather_enqueue(lo, hi)
+
+    def extract_mesh(self, min_weight: float = 1.0, window=None, mesh_savepath: str = "") -> Mesh:
+        """TSDFVolume.extract_mesh of to_dense(*window) (``window`` = (lo, hi); the tight box by default): vertices in world
+        coordinates, colours when colour was fused."""
+        lo, hi = (None, None) if window is None else window
+        return self.to_dense(lo, hi).extract_mesh(min_weight, mesh_savepath)
+
+    def raycast(self, c2w, K, H: int, W: int, near: float = 0.0, far: float = math.inf, step: Optional[float] = None,
+                min_weight: float = 1.0, normals: bool = True, color: bool = False) -> Raycast:
+        """TSDFVolume.raycast over the allocated bricks; a voxel of an unallocated brick is unobserved.  Device tensors; nothing is
+        read back."""
+        with torch.cuda.device(self.device):
+            return self.raycast_enqueue(_poses(c2w, self.device), K, H, W, near, far, step, min_weight, normals, color)
+
+
+def _grid(bounds, voxel_size: float):
+    b = np.asarray(bounds.detach().cpu() if torch.is_tensor(bounds) else bounds, np.float64).reshape(3, 2)
+    counts = np.ceil((b[:, 1] - b[:, 0]) / voxel_size)
+    if not (np.all(np.isfinite(counts)) and np.all(counts >= 0)):
+        raise ValueError(f"bounds {b.tolist()} at voxel size {voxel_size}")
+    return b, [int(c) + 1 for c in counts]
+
+
+def sparse_tsdf_mesh_from_frames(depth, c2w, K, voxel_size: float, capacity_bricks: int, trunc: Optional[float] = None, rgb=None, bounds=None,
+                                 depth_max: float = math.inf, min_weight: float = 1.0, mesh_savepath: str = "", device=None,
+                                 return_volume: bool = False, band: Optional[float] = None, views_per_call: Optional[int] = None):
+    """tsdf_mesh_from_frames with a SparseTSDFVolume of ``capacity_bricks`` slots: the grid over ``bounds`` may hold 2^31 voxels and
+    more; the mesh is marched over the tight box of the allocated bricks, which must hold fewer.  Bricks dropped for want of slots
+    are an error here: the mesh would have holes."""
+    voxel_size = float(voxel_size)
+    trunc = 4.0 * voxel_size if trunc is None else float(trunc)
+    dev = depth.device if torch.is_tensor(depth) and depth.is_cuda else _device(device)
+    with torch.cuda.device(dev):
+        D = _images(depth, dev, 0, "depth")
+        P = _poses(c2w, dev)
+        C3 = None if rgb is None else _images(rgb, dev, 3, "rgb")
+        if bounds is None:
+            bounds = frames_bounds(D, P, K, depth_max)
+            bounds[:, 0] -= trunc
+            bounds[:, 1] += trunc
+        b, dims = _grid(bounds, voxel_size)
+        vol = SparseTSDFVolume(b[:, 0], voxel_size, dims, trunc, capacity_bricks, color=C3 is not None, band=band, device=dev)
+        counts = vol.integrate(D, P, K, C3, depth_max, views_per_call)
+        if counts.dropped:
+            raise RuntimeError(f"{counts.dropped} bricks found no slot: capacity_bricks {capacity_bricks} is too small ({counts.bricks_in_use} in use)")
+        mesh = vol.extract_mesh(min_weight, mesh_savepath=mesh_savepath)
+    return (mesh, vol) if return_volume else mesh
+
+
+def sparse_tsdf_odometry(depth, K, first_pose, voxel_size: float, bounds, capacity_bricks: int, trunc: Optional[float] = None, rgb=None,
+                         min_correspondences: int = 0, device=None, color_weight: Optional[float] = None, band: Optional[float] = None,
+                         **track_kw):
+    """tsdf_odometry over a SparseTSDFVolume: frame 0 is fused at ``first_pose``; every later frame is registered against the ray
+    cast from the previous frame's pose and fused (bricks allocated first) at the pose found.  The walk is enqueued whole; one
+    read-back at the end.  A lost frame is fused at a NaN pose, which allocates and updates nothing.
+    -> (poses fp32 [n,4,4] on the host, records, SparseTSDFVolume); the records are tsdf_odometry's, and the last one also holds
+    ``dropped`` (bricks that found no slot, over all frames) and ``bricks_in_use``."""
+    if color_weight is not None and rgb is None:
+        raise ValueError("color_weight: tracking with colour needs rgb")
+    voxel_size = float(voxel_size)
+    trunc = 4.0 * voxel_size if trunc is None else float(trunc)
+    dev = depth.device if torch.is_tensor(depth) and depth.is_cuda else _device(device)
+    _, dims = _grid(bounds, voxel_size)
+    b = np.asarray(bounds.detach().cpu() if torch.is_tensor(bounds) else bounds, np.float64).reshape(3, 2)
+    with torch.cuda.device(dev):
+        D = _images(depth, dev, 0, "depth")
+        C3 = None if rgb is None else _images(rgb, dev, 3, "rgb")
+        n, H, W = D.shape
+        if n < 1:
+            raise ValueError("no frames")
+        vol = SparseTSDFVolume(b[:, 0], voxel_size, dims, trunc, capacity_bricks, color=C3 is not None, band=band, device=dev)
+        poses = torch.empty(n, 4, 4, dtype=torch.float32, device=dev)
+        words = _lib.TRACK_RESULT_DOUBLES if color_weight is None else _lib.TRACK_COLOR_RESULT_DOUBLES
+        results = torch.zeros(n, words, dtype=torch.float64, device=dev)
+        lost = torch.zeros(n, dtype=torch.bool, device=dev)
+        poses[0] = _poses(first_pose, dev)[0]
+        nan_pose = torch.full((4, 4), math.nan, dtype=torch.float32, device=dev)
+        allocs = [vol.integrate_enqueue(D[:1], poses[:1], K, None if C3 is None else C3[:1])[1]]
+        for k in range(1, n):
+            prev = poses[k - 1]
+            if color_weight is None:
+                result, pose = vol.track_enqueue(D[k], K, prev, **track_kw)
+            else:
+                result, pose = vol.track_enqueue(D[k], K, prev, rgb=C3[k], color_weight=color_weight, **track_kw)
+            bad = result[16] < float(min_correspondences)
+            poses[k] = torch.where(bad, prev, pose)
+            results[k], lost[k] = result, bad
+            allocs.append(vol.integrate_enqueue(D[k:k + 1], torch.where(bad, nan_pose, pose)[None], K, None if C3 is None else C3[k:k + 1])[1])
+        got = torch.cat([poses.reshape(n, 16).to(torch.float64), results, lost[:, None].to(torch.float64),
+                         torch.stack(allocs).to(torch.float64)], 1).cpu()
+    records = [{"transformation": r[16:32].reshape(4, 4).clone(), "n_correspondences": int(r[32]), "fitness": float(r[33]),
+                "inlier_rmse": float(r[34]), "iterations": int(r[35]), "lost": bool(r[-5])} for r in got]
+    if color_weight is not None:
+        for rec, r in zip(records, got):
+            rec["n_color"], rec["color_rmse"] = int(r[36]), float(r[37])
+    records[-1]["dropped"], records[-1]["bricks_in_use"] = int(got[:, -2].sum()), int(got[-1, -1])
+    return got[:, :16].reshape(n, 4, 4).to(torch.float32), records, vol
