@@ -448,6 +448,23 @@ SPARSE_SIGNATURES = {
 }
 
 
+# include/mipsf_sparse_mesh.h (the mesh of the sparse volume marched brick by brick; the colour of its vertices)
+SPARSE_MESH_MAX_SIDE, SPARSE_MESH_SCAN_TILE = 21474, 1024
+SPARSE_MESH_MAX_TRIS = 0x0FFFFFFF          # what the weld table of mipsf_mcubes_weld holds
+SparseMeshArgs = _args("SparseMeshArgs", [("min_weight", C.c_float), ("vol", SparseVolume), ("cases", _VP), ("offsets", _VP), ("scan", _VP),
+                                          ("soup", _VP), ("tri_slot", _VP), ("cell_ids", _VP), ("capacity_tris", _CU), ("reserved", _CU)])
+SparseMeshWeldArgs = _args("SparseMeshWeldArgs", [("T", _CU), ("capacity_tris", _CU), ("max_rounds", _CU), ("vol", SparseVolume), ("soup", _VP),
+                                                  ("tri_slot", _VP), ("scratch", _VP), ("vertices", _VP), ("faces", _VP), ("counts", _VP)])
+SparseSampleArgs = _args("SparseSampleArgs", [("m", _CU), ("vol", SparseVolume), ("points", _VP), ("out", _VP)])
+SPARSE_MESH_SIGNATURES = {
+    "mipsf_sparse_mesh_scan_words": (_U64, [_U32]),
+    "mipsf_sparse_mesh_count": (_I, [C.POINTER(SparseMeshArgs), _P]),
+    "mipsf_sparse_mesh_emit": (_I, [C.POINTER(SparseMeshArgs), _P]),
+    "mipsf_sparse_mesh_weld": (_I, [C.POINTER(SparseMeshWeldArgs), _P]),
+    "mipsf_sparse_sample": (_I, [C.POINTER(SparseSampleArgs), _P]),
+}
+
+
 # include/mipsf_image.h (two image stacks compared: error sums, valid-region SSIM and its cs term, the MS-SSIM pyramid's 2 x 2 mean)
 IMAGE_F32, IMAGE_F64 = 0, 1
 IMAGE_WINDOW, IMAGE_TILE_H, IMAGE_TILE_W, IMAGE_MAX_CHANNELS, IMAGE_MAX_SIDE = 11, 16, 32, 4, 8192
@@ -534,7 +551,8 @@ def lib() -> C.CDLL:
                                        + list(SUBMAP_SIGNATURES.items()) + list(EVAL_SIGNATURES.items())
                                        + list(RASTER_SIGNATURES.items()) + list(TSDF_SIGNATURES.items())
                                        + list(IMAGE_SIGNATURES.items()) + list(TRACK_SIGNATURES.items()) + list(TRACK_COLOR_SIGNATURES.items())
-                                       + list(SHADE_SIGNATURES.items()) + list(SPARSE_SIGNATURES.items())):
+                                       + list(SHADE_SIGNATURES.items()) + list(SPARSE_SIGNATURES.items())
+                                       + list(SPARSE_MESH_SIGNATURES.items())):
             fn = getattr(handle, name)
             fn.restype = res
             fn.argtypes = args

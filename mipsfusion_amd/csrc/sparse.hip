@@ -12,51 +12,25 @@
 // 7/8 of 15/16 of them) costs one word of the table.  The dense kernels are restated here, not shared: their code objects stay as
 // they are.
 #include "block_dev.h"
-#include "tsdf_dev.h"
-#include "../../include/mipsf_sparse.h"
+#include "sparse_dev.h"
 
 namespace mipsf {
 namespace {
 
 constexpr int TPB = 256;
 constexpr int WAVES = TPB / MIPSF_WAVE;
-constexpr uint32_t BX = MIPSF_TSDF_BRICK_X, BY = MIPSF_TSDF_BRICK_Y, BZ = MIPSF_TSDF_BRICK_Z;
-constexpr uint32_t SLOT = MIPSF_SPARSE_BRICK_VOXELS;
+constexpr uint32_t BX = BRICK_X, BY = BRICK_Y, BZ = BRICK_Z;
+constexpr uint32_t SLOT = BRICK_VOXELS;
 constexpr uint32_t RUN = 4;                       // voxels of a lane, along z
 constexpr uint32_t CHUNK = MIPSF_TSDF_VIEW_CHUNK;
 constexpr uint32_t TILE = MIPSF_TRACK_TILE;
 constexpr uint32_t UNMARKED = 0xffffffffu;
-static_assert(BX * BY * BZ == SLOT, "the words of a slot");
 static_assert(BX * BY * (BZ / RUN) == TPB, "one lane per run of the brick");
 static_assert(CHUNK == TPB, "one lane per view of a chunk");
 static_assert(TPB * SCAN_ITEMS == MIPSF_SPARSE_SCAN_TILE, "a tile of the prefix sum");
 static_assert(TILE * TILE == TPB && TILE == 16, "a lane per pixel of the tile, a wave per 8 x 8 quarter");
 static_assert((uint64_t)MIPSF_SPARSE_MAX_CAPACITY * SLOT <= 0x80000000ull, "a word offset into the pool");
 static_assert(sizeof(mipsf_sparse_alloc_record) == 32 && sizeof(mipsf_tsdf_record) == 16 && sizeof(mipsf_track_record) == 16, "records");
-
-struct Pool {
-    const double* ticks[3];
-    int32_t* table;
-    int32_t* slot_brick;
-    uint32_t* birth;
-    uint32_t* count;
-    float* tsdf;
-    float* weight;
-    float* color;
-    uint32_t X, Y, Z, capacity;
-    uint32_t bricks_y, bricks_z, bricks;
-    double origin[3], voxel;
-};
-
-__device__ __forceinline__ uint32_t brick_of(const Pool& v, uint32_t i, uint32_t j, uint32_t k) {
-    return ((i / BX) * v.bricks_y + j / BY) * v.bricks_z + k / BZ;             // below 2^31: the host refuses more bricks
-}
-
-// the word of voxel (i, j, k) in the pool, or -1: its brick has no slot
-__device__ __forceinline__ int32_t word_of(const Pool& v, uint32_t i, uint32_t j, uint32_t k) {
-    const int32_t slot = v.table[brick_of(v, i, j, k)];
-    return slot < 0 ? -1 : (int32_t)((uint32_t)slot * SLOT + ((i % BX) * BY + j % BY) * BZ + k % BZ);
-}
 
 // p[0..n) = value.  The clears of a call are launches of this kernel, not memset nodes: a captured graph replays them as it
 // replays the kernels around them.
@@ -439,29 +413,6 @@ __device__ __forceinline__ bool field_of(const Pool& v, const Cast& s, double px
     return b.valid && field_at(v, s, b, f);
 }
 
-// the rule of mipsf_tsdf_sample (tsdf_dev.h states it for dense arrays) with the corner reads through the table
-__device__ __forceinline__ void sample_color(const Pool& v, double x, double y, double z, float res[3]) {
-    res[0] = res[1] = res[2] = 0.0f;
-    if (fabs(x) < INFINITY && fabs(y) < INFINITY && fabs(z) < INFINITY) {
-        const TsdfAxis ax = tsdf_axis_of(x, v.X), ay = tsdf_axis_of(y, v.Y), az = tsdf_axis_of(z, v.Z);
-        double den = 0.0, num[3] = {0.0, 0.0, 0.0};
-#pragma unroll
-        for (int corner = 0; corner < 8; ++corner) {
-            const bool a = corner & 4, b = corner & 2, c = corner & 1;
-            const double share = ((a ? ax.f : 1.0 - ax.f) * (b ? ay.f : 1.0 - ay.f)) * (c ? az.f : 1.0 - az.f);
-            const int32_t at = word_of(v, a ? ax.i1 : ax.i0, b ? ay.i1 : ay.i0, c ? az.i1 : az.i0);
-            const double mshare = (at < 0 ? 0.0f : v.weight[at]) > 0.0f ? share : 0.0;
-            den = den + mshare;
-#pragma unroll
-            for (int ch = 0; ch < 3; ++ch) num[ch] = num[ch] + mshare * (double)(at < 0 ? 0.0f : v.color[(size_t)at * 3 + ch]);
-        }
-        if (den > 0.0) {
-#pragma unroll
-            for (int ch = 0; ch < 3; ++ch) res[ch] = (float)(num[ch] / den);
-        }
-    }
-}
-
 // grid: (tiles of a view, n)
 MIPSF_SINGLE_FP32 __global__ void __launch_bounds__(TPB) sparse_raycast_kernel(Pool v, Cast s, float* __restrict__ depth, float* __restrict__ normals,
                                                                                float* __restrict__ color_out, mipsf_track_record* __restrict__ record) {
@@ -558,39 +509,6 @@ MIPSF_SINGLE_FP32 __global__ void __launch_bounds__(TPB) sparse_raycast_kernel(P
 }
 
 // ------------------------------------------------------------------------------------------------ host
-bool pos_finite(double x) { return x > 0.0 && x < INFINITY; }
-bool is_finite(double x) { return fabs(x) < INFINITY; }
-
-uint64_t brick_count(uint32_t X, uint32_t Y, uint32_t Z) { return (uint64_t)blocks_for(X, BX) * blocks_for(Y, BY) * blocks_for(Z, BZ); }
-
-// what every entry point refuses of the volume; 0: fine
-int volume_ok(const mipsf_sparse_volume& g, const char* who) {
-    MIPSF_REQUIRE(g.X > 0 && g.Y > 0 && g.Z > 0, "%s: a grid of %u x %u x %u has no voxels", who, g.X, g.Y, g.Z);
-    // three factors below 2^29 each: the product of the first two fits 64 bits, and is compared before the third comes in
-    const uint64_t xy = (uint64_t)blocks_for(g.X, BX) * blocks_for(g.Y, BY);
-    MIPSF_REQUIRE(xy <= MIPSF_SPARSE_MAX_BRICKS && xy * blocks_for(g.Z, BZ) <= MIPSF_SPARSE_MAX_BRICKS,
-                  "%s: a grid of %u x %u x %u voxels has 2^31 bricks or more", who, g.X, g.Y, g.Z);
-    MIPSF_REQUIRE(g.capacity > 0 && g.capacity <= MIPSF_SPARSE_MAX_CAPACITY, "%s: capacity %u, from 1 to %u slots", who, g.capacity,
-                  MIPSF_SPARSE_MAX_CAPACITY);
-    MIPSF_REQUIRE(pos_finite(g.voxel), "%s: voxel %g is not positive and finite", who, g.voxel);
-    MIPSF_REQUIRE(is_finite(g.origin[0]) && is_finite(g.origin[1]) && is_finite(g.origin[2]), "%s: origin %g %g %g", who, g.origin[0], g.origin[1],
-                  g.origin[2]);
-    MIPSF_REQUIRE(g.ticks[0] && g.ticks[1] && g.ticks[2] && g.table && g.slot_brick && g.birth && g.count && g.tsdf && g.weight,
-                  "%s: null pointer in the volume", who);
-    return 0;
-}
-
-Pool pool_of(const mipsf_sparse_volume& g) {
-    Pool v;
-    for (int d = 0; d < 3; ++d) v.ticks[d] = g.ticks[d], v.origin[d] = g.origin[d];
-    v.table = g.table, v.slot_brick = g.slot_brick, v.birth = g.birth, v.count = g.count;
-    v.tsdf = g.tsdf, v.weight = g.weight, v.color = g.color;
-    v.X = g.X, v.Y = g.Y, v.Z = g.Z, v.capacity = g.capacity;
-    v.bricks_y = blocks_for(g.Y, BY), v.bricks_z = blocks_for(g.Z, BZ), v.bricks = (uint32_t)brick_count(g.X, g.Y, g.Z);
-    v.voxel = g.voxel;
-    return v;
-}
-
 int images_ok(uint32_t n, uint32_t H, uint32_t W, double fx, double fy, double cx, double cy, const char* who) {
     MIPSF_REQUIRE(n == 0 || (H > 0 && W > 0), "%s: an image of %u x %u has no pixels", who, H, W);
     MIPSF_REQUIRE(H <= MIPSF_TSDF_MAX_SIDE && W <= MIPSF_TSDF_MAX_SIDE, "%s: image %u x %u, at most %u a side", who, H, W, MIPSF_TSDF_MAX_SIDE);

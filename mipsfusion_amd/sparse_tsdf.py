@@ -4,13 +4,15 @@ a slot when a depth pixel of a fused view lands within ``band`` of it; only allo
 kernels are those of ``csrc/sparse.hip`` (C ABI: include/mipsf_sparse.h):
 
     SparseTSDFVolume               the state (index grid, pool of tsdf, weight, optionally colour; all on the device) and integrate /
-                                   to_dense / extract_mesh / raycast / track / reset
+                                   to_dense / extract_mesh / extract_mesh_bricks / raycast / track / reset
     sparse_tsdf_mesh_from_frames   depth frames + poses -> mesh.Mesh, the namesake of tsdf_mesh_from_frames
     sparse_tsdf_odometry           depth frames -> poses, the namesake of tsdf_odometry
 
 Every output is the dense volume's rule read over the dense state with the voxels of unallocated bricks left at zero, and EQUALS the
-float64 restatement in tests/sparse_cpu.py.  Meshing goes through ``to_dense``: a window of the grid as a TSDFVolume, so a window of
-2^31 voxels is still the limit of one marching call.  Nothing is ever freed.  There is no CPU fallback.
+float64 restatement in tests/sparse_cpu.py.  ``extract_mesh`` goes through ``to_dense``: a window of the grid as a TSDFVolume, below
+2^31 voxels a marching call.  ``extract_mesh_bricks`` marches the allocated bricks themselves (csrc/sparse_mesh.hip,
+include/mipsf_sparse_mesh.h): the whole volume in one call whatever the size of the virtual grid, and EQUALS
+tests/sparse_mesh_cpu.py.  Nothing is ever freed.  There is no CPU fallback.
 """
 from __future__ import annotations
 
@@ -22,7 +24,7 @@ import numpy as np
 import torch
 
 from . import _lib
-from .mesh import Mesh
+from .mesh import Mesh, filter_faces, save_ply
 from .mesh_render import _poses
 from .scene_mesh import _intrinsics
 from .tsdf import Raycast, TSDFVolume, _device, _images, frames_bounds
@@ -250,6 +252,91 @@ class SparseTSDFVolume:
         lo, hi = (None, None) if window is None else window
         return self.to_dense(lo, hi).extract_mesh(min_weight, mesh_savepath)
 
+    # ----------------------------------------------------------------------------------------------------------- brick by brick
+    def _mesh_args(self, min_weight: float):
+        """mipsf_sparse_mesh_count enqueued -> (argument block, cases uint8 [capacity,1024], offsets int32 [capacity + 1])"""
+        lib = _lib.lib()
+        cases = torch.empty(self.capacity, _lib.SPARSE_BRICK_VOXELS, dtype=torch.uint8, device=self.device)
+        offsets = torch.empty(self.capacity + 1, dtype=torch.int32, device=self.device)
+        scan = torch.empty(int(lib.mipsf_sparse_mesh_scan_words(self.capacity)) // 2, dtype=torch.int64, device=self.device)
+        a = _lib.SparseMeshArgs.new(min_weight=float(min_weight), vol=self._vol, cases=_lib.dptr(cases, torch.uint8),
+                                    offsets=_lib.dptr(offsets, torch.int32), scan=_lib.dptr(scan, torch.int64))
+        _lib.check(lib.mipsf_sparse_mesh_count(C.byref(a), _lib.stream_ptr()), "sparse_mesh_count")
+        return a, cases, offsets
+
+    def brick_soup_enqueue(self, min_weight: float = 1.0, return_cells: bool = False):
+        """The triangle soup of the allocated bricks in slot order (mipsf_sparse_mesh_count, one read-back of the triangle count T,
+        mipsf_sparse_mesh_emit) -> soup fp32 [T,3,3] in the coordinates of each brick's block (the brick plus one voxel on every side:
+        index units minus the brick's base (8bx-1, 8by-1, 16bz-1)), tri_slot int32 [T], offsets int32 [capacity + 1] (the first
+        triangle of every slot; offsets[capacity] = T) (, the cell within the brick int32 [T]); all on the device."""
+        with torch.cuda.device(self.device):
+            a, cases, offsets = self._mesh_args(min_weight)
+            T = int(offsets[-1]) & 0xFFFFFFFF               # the one read-back the soup's size needs
+            if T > _lib.SPARSE_MESH_MAX_TRIS:
+                raise RuntimeError(f"the soup of the bricks has {T} triangles or more, at most {_lib.SPARSE_MESH_MAX_TRIS} can be welded")
+            soup = torch.empty((T, 3, 3), dtype=torch.float32, device=self.device)
+            tri_slot = torch.empty((T,), dtype=torch.int32, device=self.device)
+            cells = torch.empty((T,), dtype=torch.int32, device=self.device) if return_cells else None
+            if T:
+                a.soup, a.tri_slot, a.cell_ids, a.capacity_tris = _lib.dptr(soup), _lib.dptr(tri_slot, torch.int32), _lib.dptr(cells, torch.int32), T
+                _lib.check(_lib.lib().mipsf_sparse_mesh_emit(C.byref(a), _lib.stream_ptr()), "sparse_mesh_emit")
+        return (soup, tri_slot, offsets) + ((cells,) if return_cells else ())
+
+    def weld_bricks(self, soup: torch.Tensor, tri_slot: torch.Tensor, max_rounds: int = 2):
+        """mipsf_sparse_mesh_weld: the soup of brick_soup_enqueue welded on the global 1e-5 grid -> vertices float64 [V,3] in index
+        units of the virtual grid, numbered by first appearance, faces int32 [T,3]; one read-back (V) per attempt, as mesh.weld"""
+        T = soup.shape[0]
+        with torch.cuda.device(self.device):
+            scratch = torch.empty(_lib.buffer_size(_lib.SIZE_MCUBES_WELD_WORDS, T) // 2 + 1, dtype=torch.int64, device=self.device)
+            vertices = torch.empty((3 * T, 3), dtype=torch.float64, device=self.device)
+            faces = torch.empty((T, 3), dtype=torch.int32, device=self.device)
+            counts = torch.empty(4, dtype=torch.int32, device=self.device)
+            while True:
+                a = _lib.SparseMeshWeldArgs.new(T=T, capacity_tris=T, max_rounds=max_rounds, vol=self._vol, soup=_lib.dptr(soup) if T else None,
+                                                tri_slot=_lib.dptr(tri_slot, torch.int32) if T else None, scratch=_lib.dptr(scratch, torch.int64),
+                                                vertices=_lib.dptr(vertices, torch.float64) if T else None,
+                                                faces=_lib.dptr(faces, torch.int32) if T else None, counts=_lib.dptr(counts, torch.int32))
+                _lib.check(_lib.lib().mipsf_sparse_mesh_weld(C.byref(a), _lib.stream_ptr()), "sparse_mesh_weld")
+                V, moved, unplaced, _ = counts.tolist()
+                if unplaced:
+                    raise RuntimeError(f"sparse_mesh_weld: {unplaced} soup vertices without a brick or with a cell outside the weld grid")
+                if moved < max_rounds:
+                    break
+                if max_rounds >= 64:
+                    raise RuntimeError("sparse_mesh_weld: labels still moving after 64 rounds (a chain of more than 64 weld cells)")
+                max_rounds = min(64, 4 * max_rounds)            # a chain of clusters longer than the rounds: go on
+        return vertices[:V], faces
+
+    def sample_enqueue(self, points: torch.Tensor) -> torch.Tensor:
+        """points float64 [m,3] in index units of the virtual grid, on the device -> colour fp32 [m,3] on the device
+        (mipsf_sparse_sample)"""
+        if self.color is None:
+            raise ValueError("the volume was made without colour")
+        if points.dim() != 2 or points.shape[1] != 3:
+            raise ValueError(f"points: expected [m,3], got {tuple(points.shape)}")
+        m = points.shape[0]
+        with torch.cuda.device(self.device):
+            out = torch.empty(max(m, 1), 3, dtype=torch.float32, device=self.device)[:m]
+            a = _lib.SparseSampleArgs.new(m=m, vol=self._vol, points=_lib.dptr(points, torch.float64), out=out.data_ptr())
+            _lib.check(_lib.lib().mipsf_sparse_sample(C.byref(a), _lib.stream_ptr()), "sparse_sample")
+        return out
+
+    def extract_mesh_bricks(self, min_weight: float = 1.0, mesh_savepath: str = "") -> Mesh:
+        """The mesh of the WHOLE volume, marched brick by brick: no dense window is formed and the virtual grid may hold 2^31 voxels
+        and more (a side of at most 21474 voxels: the weld's cells are 32-bit).  The marching volume is tsdf where the brick has a
+        slot and weight >= min_weight, off elsewhere; isovalue 0, truncation 1 and the face filters are TSDFVolume.extract_mesh's.
+        Two read-backs, the triangle count and the vertex count.  -> Mesh with world vertices in float64 (origin + index * voxel_size,
+        the index exact), faces int64, and per-vertex colours when colour was fused."""
+        with torch.cuda.device(self.device):
+            soup, tri_slot, _ = self.brick_soup_enqueue(min_weight)
+            v, f = self.weld_bricks(soup, tri_slot)
+            f = filter_faces(f)[0].to(torch.int64)
+            colors = None if self.color is None else self.sample_enqueue(v.contiguous()).cpu().numpy()
+        mesh = Mesh(self.origin + v.cpu().numpy() * self.voxel_size, f.cpu().numpy(), colors)
+        if mesh_savepath:
+            save_ply(mesh_savepath, mesh.vertices, mesh.faces, mesh.vertex_colors)
+        return mesh
+
     def raycast(self, c2w, K, H: int, W: int, near: float = 0.0, far: float = math.inf, step: Optional[float] = None,
                 min_weight: float = 1.0, normals: bool = True, color: bool = False) -> Raycast:
         """TSDFVolume.raycast over the allocated bricks; a voxel of an unallocated brick is unobserved.  Device tensors; nothing is
@@ -268,10 +355,11 @@ def _grid(bounds, voxel_size: float):
 
 def sparse_tsdf_mesh_from_frames(depth, c2w, K, voxel_size: float, capacity_bricks: int, trunc: Optional[float] = None, rgb=None, bounds=None,
                                  depth_max: float = math.inf, min_weight: float = 1.0, mesh_savepath: str = "", device=None,
-                                 return_volume: bool = False, band: Optional[float] = None, views_per_call: Optional[int] = None):
+                                 return_volume: bool = False, band: Optional[float] = None, views_per_call: Optional[int] = None,
+                                 bricks: bool = False):
     """tsdf_mesh_from_frames with a SparseTSDFVolume of ``capacity_bricks`` slots: the grid over ``bounds`` may hold 2^31 voxels and
-    more; the mesh is marched over the tight box of the allocated bricks, which must hold fewer.  Bricks dropped for want of slots
-    are an error here: the mesh would have holes."""
+    more; the mesh is marched over the tight box of the allocated bricks, which must hold fewer, or with ``bricks`` brick by brick
+    (extract_mesh_bricks), which has no such limit.  Bricks dropped for want of slots are an error here: the mesh would have holes."""
     voxel_size = float(voxel_size)
     trunc = 4.0 * voxel_size if trunc is None else float(trunc)
     dev = depth.device if torch.is_tensor(depth) and depth.is_cuda else _device(device)
@@ -288,7 +376,7 @@ def sparse_tsdf_mesh_from_frames(depth, c2w, K, voxel_size: float, capacity_bric
         counts = vol.integrate(D, P, K, C3, depth_max, views_per_call)
         if counts.dropped:
             raise RuntimeError(f"{counts.dropped} bricks found no slot: capacity_bricks {capacity_bricks} is too small ({counts.bricks_in_use} in use)")
-        mesh = vol.extract_mesh(min_weight, mesh_savepath=mesh_savepath)
+        mesh = vol.extract_mesh_bricks(min_weight, mesh_savepath) if bricks else vol.extract_mesh(min_weight, mesh_savepath=mesh_savepath)
     return (mesh, vol) if return_volume else mesh
 
 
