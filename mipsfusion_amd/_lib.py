@@ -375,6 +375,18 @@ TSDF_SIGNATURES = {
 }
 
 
+# include/mipsf_deintegrate.h (views taken out of the TSDF volume again: the inverse of mipsf_tsdf_integrate's running mean)
+DEINTEGRATE_RECORD_WORDS = 4               # uint64 removed, missing, emptied, observed
+DeintegrateArgs = _args("DeintegrateArgs", [("X", _CU), ("Y", _CU), ("Z", _CU), ("n", _CU), ("H", _CU), ("W", _CU), ("flags", _CU),
+                                            ("fx", C.c_double), ("fy", C.c_double), ("cx", C.c_double), ("cy", C.c_double),
+                                            ("trunc", C.c_double), ("depth_max", C.c_double),
+                                            ("ticks", _VP * 3), ("depth", _VP), ("rgb", _VP), ("poses", _VP), ("tsdf", _VP),
+                                            ("weight", _VP), ("color", _VP), ("record", _VP)])
+DEINTEGRATE_SIGNATURES = {
+    "mipsf_deintegrate_views": (_I, [C.POINTER(DeintegrateArgs), _P]),
+}
+
+
 # include/mipsf_track.h (the volume as depth, normal and colour images by ray casting; a depth frame registered against them)
 TRACK_MAX_SAMPLES, TRACK_TILE, TRACK_RESULT_DOUBLES, TRACK_MAX_ITERATION, TRACK_MAX_VIEWS = 0x100000, 16, 20, 1000, 65535
 TRACK_NO_SKIP = 1
@@ -552,7 +564,7 @@ def lib() -> C.CDLL:
                                        + list(RASTER_SIGNATURES.items()) + list(TSDF_SIGNATURES.items())
                                        + list(IMAGE_SIGNATURES.items()) + list(TRACK_SIGNATURES.items()) + list(TRACK_COLOR_SIGNATURES.items())
                                        + list(SHADE_SIGNATURES.items()) + list(SPARSE_SIGNATURES.items())
-                                       + list(SPARSE_MESH_SIGNATURES.items())):
+                                       + list(SPARSE_MESH_SIGNATURES.items()) + list(DEINTEGRATE_SIGNATURES.items())):
             fn = getattr(handle, name)
             fn.restype = res
             fn.argtypes = args

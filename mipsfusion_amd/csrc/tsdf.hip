@@ -7,7 +7,8 @@
 // 256: one lane per view tests the brick's bounding sphere against the view, the survivors' indices go to LDS in ascending order
 // (the update is order-dependent by definition), and every lane walks that list; the pose of a view is read through a
 // wave-uniform index.  The sphere test is the only arithmetic here that the header does not fix: it may be generous, it must
-// never leave out a pair the rule updates.  The projection is stated a second time here, next to raster.hip's.
+// never leave out a pair the rule updates.  The projection is stated a second time, next to raster.hip's: in tsdf_dev.h, with the
+// sphere test, where tsdf_remove.hip takes the same views out of the same voxels again.
 #include "block_dev.h"
 #include "tsdf_dev.h"
 
@@ -23,64 +24,8 @@ static_assert(BX * BY * (BZ / RUN) == TPB, "one lane per run of the brick");
 static_assert(CHUNK == TPB, "one lane per view of a chunk");
 static_assert(sizeof(mipsf_tsdf_record) == 16, "tsdf record");
 
-struct Frames {
-    const float* depth;
-    const float* rgb;
-    const float* poses;
-    uint32_t n, H, W, flags;
-    double fx, fy, cx, cy, trunc, depth_max, max_weight;
-};
-
-struct Volume {
-    const double* ticks[3];
-    float* tsdf;
-    float* weight;
-    float* color;
-    uint32_t X, Y, Z;
-    uint32_t bricks_y, bricks_z;
-};
-
-// Whether view k can update a voxel of the ball (centre c, radius r) that holds the brick.  With cc the centre in the camera frame
-// and a point of the ball at most r_c = r * |column c of R| from it along camera axis c (Cauchy-Schwarz on the header's
-// cam[c] = column c of R . q), a pair can update only when
-//   z > 0                       ->  zc + r_z > 0
-//   z <= d + trunc <= depth_max + trunc  ->  zc - r_z <= depth_max + trunc
-//   -0.5 <= u < W - 0.5         ->  x - a0 z >= 0 and x - a1 z <= 0 with a0 = (-1.5 - cx)/fx, a1 = (W + 0.5 - cx)/fx, and the like for v
-// The image is so taken a pixel wider on every side, and r a millionth larger plus 1e-9 of the scene's scale, which is many orders
-// above the rounding of the rule's own u, v and z (relative 1e-15) wherever the rule's z is large enough to land in the image at
-// all; where it is not, the voxel is within rounding of the camera centre, the ball holds the centre and every test passes.  A
-// pose with an entry that is not finite updates nothing (cam, u or v is then infinite or NaN for every voxel, or z is and
-// sdf = -inf) and is left out.  NaN ticks among finite ones are ignored by the box (fmin, fmax): their voxels
-// project nowhere.
-__device__ __forceinline__ bool view_can_update(const Frames& s, uint32_t k, const double c[3], double r) {
-    const float* P = s.poses + (size_t)k * 16;
-    double R[9], t[3], scale = 1.0;
-    bool finite = true;
-#pragma unroll
-    for (int i = 0; i < 3; ++i) {
-        R[i * 3] = (double)P[i * 4], R[i * 3 + 1] = (double)P[i * 4 + 1], R[i * 3 + 2] = (double)P[i * 4 + 2];
-        t[i] = (double)P[i * 4 + 3];
-        finite = finite && fabs(R[i * 3]) < INFINITY && fabs(R[i * 3 + 1]) < INFINITY && fabs(R[i * 3 + 2]) < INFINITY && fabs(t[i]) < INFINITY;
-        scale += fabs(t[i]) + fabs(c[i]);
-    }
-    if (!finite) return false;
-    const double q[3] = {c[0] - t[0], c[1] - t[1], c[2] - t[2]};
-    const double rr = r * 1.000001 + 1.0e-9 * scale;
-    double cc[3], rc[3];
-#pragma unroll
-    for (int a = 0; a < 3; ++a) {
-        cc[a] = (R[a] * q[0] + R[3 + a] * q[1]) + R[6 + a] * q[2];
-        rc[a] = rr * sqrt((R[a] * R[a] + R[3 + a] * R[3 + a]) + R[6 + a] * R[6 + a]) * 1.000001;
-    }
-    const double zc = -cc[2];
-    bool keep = zc + rc[2] > 0.0 && zc - rc[2] <= s.depth_max + s.trunc;
-    const double a0 = (-1.5 - s.cx) / s.fx, a1 = ((double)s.W + 0.5 - s.cx) / s.fx;
-    keep = keep && (cc[0] - a0 * zc) + (rc[0] + fabs(a0) * rc[2]) >= 0.0 && (cc[0] - a1 * zc) - (rc[0] + fabs(a1) * rc[2]) <= 0.0;
-    // v = cy - fy*(y/z) in [-1.5, H + 0.5]  ->  y/z in [b0, b1] = [(cy - H - 0.5)/fy, (cy + 1.5)/fy]
-    const double b0 = (s.cy - (double)s.H - 0.5) / s.fy, b1 = (s.cy + 1.5) / s.fy;
-    keep = keep && (cc[1] - b0 * zc) + (rc[1] + fabs(b0) * rc[2]) >= 0.0 && (cc[1] - b1 * zc) - (rc[1] + fabs(b1) * rc[2]) <= 0.0;
-    return keep;
-}
+using Frames = TsdfFrames;                        // tsdf_dev.h: the views, the volume, the ball test and the projection, shared with
+using Volume = TsdfGrid;                          // tsdf_remove.hip
 
 // grid: one block per brick, bricks in (x, y, z) order with z fastest
 template <bool COLOR>
@@ -114,28 +59,17 @@ MIPSF_SINGLE_FP32 __global__ void __launch_bounds__(TPB) tsdf_integrate_kernel(V
         }
     }
 
-    // the ball that holds the brick's voxels: the box of their positions, its centre and half its diagonal (every lane the same)
+    // the ball that holds the brick's voxels (every lane the same); a brick without one takes every view
     double c[3], radius;
-    {
-        double lo[3] = {INFINITY, INFINITY, INFINITY}, hi[3] = {-INFINITY, -INFINITY, -INFINITY};
-        for (uint32_t a = x0; a < x1; ++a) lo[0] = fmin(lo[0], (double)(float)vol.ticks[0][a]), hi[0] = fmax(hi[0], (double)(float)vol.ticks[0][a]);
-        for (uint32_t a = y0; a < y1; ++a) lo[1] = fmin(lo[1], (double)(float)vol.ticks[1][a]), hi[1] = fmax(hi[1], (double)(float)vol.ticks[1][a]);
-        for (uint32_t a = z0; a < z1; ++a) lo[2] = fmin(lo[2], (double)(float)vol.ticks[2][a]), hi[2] = fmax(hi[2], (double)(float)vol.ticks[2][a]);
-        double h[3];
-#pragma unroll
-        for (int a = 0; a < 3; ++a) c[a] = 0.5 * lo[a] + 0.5 * hi[a], h[a] = fmax(hi[a] - c[a], c[a] - lo[a]);
-        radius = sqrt((h[0] * h[0] + h[1] * h[1]) + h[2] * h[2]);
-    }
-    // a tick that is infinite (or NaN on a whole axis) leaves no ball to test: such a brick takes every view
-    const bool cull = !(s.flags & MIPSF_TSDF_NO_CULL) && fabs(c[0]) < INFINITY && fabs(c[1]) < INFINITY && fabs(c[2]) < INFINITY && radius < INFINITY;
+    const bool ball = tsdf_brick_ball(vol, x0, x1, y0, y1, z0, z1, c, radius);
+    const bool cull = !(s.flags & MIPSF_TSDF_NO_CULL) && ball;
 
-    const double w_lim = (double)s.W, h_lim = (double)s.H;
     const size_t hw = (size_t)s.H * s.W;
     uint64_t updates = 0;
     for (uint32_t first = 0; first < s.n; first += CHUNK) {
         // ---- which views of the chunk can reach the brick, in ascending order
         const uint32_t k = first + tid;
-        const bool keep = k < s.n && (!cull || view_can_update(s, k, c, radius));
+        const bool keep = k < s.n && (!cull || tsdf_view_can_update(s, k, c, radius));
         const uint64_t mask = __ballot(keep);
         __syncthreads();                                                        // the list of the chunk before is read no more
         if (lane == 0) wave_count[wave] = (uint32_t)__popcll(mask);
@@ -154,26 +88,12 @@ MIPSF_SINGLE_FP32 __global__ void __launch_bounds__(TPB) tsdf_integrate_kernel(V
             const uint32_t view = __builtin_amdgcn_readfirstlane(list[e]);
             const float* P = s.poses + (size_t)view * 16;
             const float* D = s.depth + (size_t)view * hw;
-            const double qx = px - (double)P[3], qy = py - (double)P[7], tz = (double)P[11];
-            const double r20 = (double)P[8], r21 = (double)P[9], r22 = (double)P[10];
-            const double pre0 = (double)P[0] * qx + (double)P[4] * qy;
-            const double pre1 = (double)P[1] * qx + (double)P[5] * qy;
-            const double pre2 = (double)P[2] * qx + (double)P[6] * qy;
+            const TsdfViewRow row = tsdf_view_row(P, px, py);
 #pragma unroll
             for (uint32_t r = 0; r < RUN; ++r) {
-                const double qz = pz[r] - tz;
-                const double cam0 = pre0 + r20 * qz, cam1 = pre1 + r21 * qz, cam2 = pre2 + r22 * qz;
-                const double z = -cam2;
-                const double u = s.cx + s.fx * (cam0 / z);
-                const double v = s.cy - s.fy * (cam1 / z);
-                const double col = floor(u + 0.5), row = floor(v + 0.5);
-                if (!(ok[r] && z > 0.0 && col >= 0.0 && col < w_lim && row >= 0.0 && row < h_lim)) continue;
-                const size_t pixel = (size_t)(uint32_t)row * s.W + (uint32_t)col;
-                const double d = (double)D[pixel];
-                const double sdf = d - z;
-                if (!(d > 0.0 && d < INFINITY && d <= s.depth_max && sdf >= -s.trunc)) continue;
-                double val = sdf / s.trunc;
-                if (val > 1.0) val = 1.0;
+                size_t pixel;
+                double val;
+                if (!(ok[r] && tsdf_view_hits(s, row, D, pz[r], pixel, val))) continue;
                 const double w0 = (double)weight[r], w1 = w0 + 1.0;
                 tsdf[r] = (float)((((double)tsdf[r]) * w0 + val) / w1);
                 if (COLOR) {

@@ -9,6 +9,8 @@ DESIGN.md 4.19):
                                against such images); kernels of ``csrc/tsdf_track.hip``, C ABI include/mipsf_track.h, DESIGN.md 4.21
                                track(rgb=...) adds a photometric row per pair against the ray cast's colour, which holds the pose
                                along walls: ``csrc/track_color.hip``, include/mipsf_track_color.h, DESIGN.md 4.23
+                               deintegrate / reintegrate take fused views out again and fuse them at new poses, the step after a
+                               loop closure: ``csrc/tsdf_remove.hip``, include/mipsf_deintegrate.h, DESIGN.md 4.26
     tsdf_odometry              depth frames -> poses: every frame registered against the ray cast of the volume, then fused
     tsdf_mesh_from_frames      depth frames + poses -> mesh.Mesh
     mesh_from_rendered_depth   model + poses -> rendered depth -> mesh.Mesh
@@ -34,6 +36,19 @@ from .scene_mesh import _intrinsics
 class TSDFCounts(NamedTuple):
     updates: int                     # (voxel, view) pairs that updated, over the calls of one integrate()
     observed: int                    # voxels whose weight is positive afterwards
+
+
+class RemoveCounts(NamedTuple):
+    removed: int                     # (voxel, view) pairs taken out, over the calls of one deintegrate()
+    missing: int                     # pairs the views hit whose voxel had no positive weight left (a diagnostic, not a guarantee)
+    emptied: int                     # removals that brought a voxel back to the never-observed state
+    observed: int                    # voxels whose weight is positive afterwards
+
+
+class ReintegrateCounts(NamedTuple):
+    views_moved: int                 # views removed at their old pose and fused at their new one
+    removed: RemoveCounts
+    fused: TSDFCounts
 
 
 class Raycast(NamedTuple):
@@ -93,6 +108,25 @@ def _images(a, dev, channels: int, what: str) -> torch.Tensor:
     return a.to(dev).to(torch.float32).contiguous()
 
 
+def _moved(old: np.ndarray, new: np.ndarray, min_translation: float, min_rotation: float) -> np.ndarray:
+    """fp32 poses [n,4,4] before and after -> bool [n], in float64: the translation changed by more than min_translation, or the
+    rotation by more than min_rotation; with both at 0, any word of the pose differs.  The angle between two rotations is taken
+    from their difference, 2 asin(|R_new - R_old|_F / (2 sqrt 2)): exact for rotation matrices, exactly 0 for equal words and
+    proportional to the difference near 0, where the arc cosine of the trace turns a rounding of 1e-7 into 4e-4 rad.  A pose
+    that is not finite (a lost frame, which fused nothing) on one side only counts as moved; on both sides, as not."""
+    if min_translation < 0 or min_rotation < 0 or math.isnan(min_translation) or math.isnan(min_rotation):
+        raise ValueError(f"min_translation {min_translation} and min_rotation {min_rotation} must not be negative")
+    if min_translation == 0.0 and min_rotation == 0.0:
+        return (np.ascontiguousarray(old).view(np.uint32) != np.ascontiguousarray(new).view(np.uint32)).reshape(len(old), -1).any(1)
+    a, b = old.astype(np.float64), new.astype(np.float64)
+    fine_a, fine_b = np.isfinite(a[:, :3]).all((1, 2)), np.isfinite(b[:, :3]).all((1, 2))
+    with np.errstate(all="ignore"):
+        shift = np.sqrt(((b[:, :3, 3] - a[:, :3, 3]) ** 2).sum(1))
+        chord = np.sqrt(((b[:, :3, :3] - a[:, :3, :3]) ** 2).sum((1, 2)))
+        turn = 2.0 * np.arcsin(np.minimum(chord / (2.0 * math.sqrt(2.0)), 1.0))
+        return (fine_a != fine_b) | (fine_a & fine_b & ((shift > min_translation) | (turn > min_rotation)))
+
+
 class TSDFVolume:
     """A dense TSDF volume on the device.  Voxel (i,j,k) sits at origin + voxel_size * (i,j,k) (float64, rounded to fp32 by the
     kernel); ``trunc`` is the truncation distance in metres.  tsdf is in units of trunc: 1 in free space, 0 on the surface,
@@ -149,6 +183,51 @@ class TSDFVolume:
                 a.ticks[d] = _lib.dptr(self._ticks_dev[d], torch.float64)
             _lib.check(_lib.lib().mipsf_tsdf_integrate(C.byref(a), _lib.stream_ptr()), "tsdf_integrate")
         return record
+
+    def _removable(self) -> None:
+        if math.isfinite(self.max_weight):
+            raise ValueError(f"views cannot be removed from a volume made with max_weight {self.max_weight}: a capped running mean is a "
+                             f"moving average, which has no inverse; make the volume with max_weight=inf")
+
+    def deintegrate_enqueue(self, depth: torch.Tensor, poses: torch.Tensor, K, rgb: Optional[torch.Tensor] = None,
+                            depth_max: float = math.inf, record: Optional[torch.Tensor] = None, flags: int = 0) -> torch.Tensor:
+        """One launch of mipsf_deintegrate_views, the inverse of integrate_enqueue for views fused with these very arguments;
+        nothing is read back.  depth fp32 [n,H,W], poses fp32 [n,4,4], rgb fp32 [n,H,W,3] or None, all on the device -> record
+        int64 [4] on the device: pairs removed, pairs missing, voxels emptied, voxels with a positive weight"""
+        self._removable()
+        _lib.dptr(depth), _lib.dptr(poses), _lib.dptr(rgb)
+        if depth.dim() != 3 or tuple(poses.shape) != (depth.shape[0], 4, 4):
+            raise ValueError(f"expected depth [n,H,W] and poses [n,4,4], got {tuple(depth.shape)} and {tuple(poses.shape)}")
+        if rgb is not None and tuple(rgb.shape) != tuple(depth.shape) + (3,):
+            raise ValueError(f"rgb: expected {tuple(depth.shape) + (3,)}, got {tuple(rgb.shape)}")
+        if (rgb is None) != (self.color is None):
+            raise ValueError("rgb goes with a volume made with color=True, and such a volume needs rgb")
+        fx, fy, cx, cy = (float(x) for x in _intrinsics(K))
+        n, H, W = depth.shape
+        with torch.cuda.device(self.device):
+            record = torch.empty(_lib.DEINTEGRATE_RECORD_WORDS, dtype=torch.int64, device=self.device) if record is None else record
+            a = _lib.DeintegrateArgs.new(X=self.dims[0], Y=self.dims[1], Z=self.dims[2], n=n, H=H, W=W, flags=int(flags), fx=fx, fy=fy,
+                                         cx=cx, cy=cy, trunc=self.trunc, depth_max=float(depth_max),
+                                         depth=depth.data_ptr(), rgb=None if rgb is None else rgb.data_ptr(), poses=poses.data_ptr(),
+                                         tsdf=_lib.dptr(self.tsdf), weight=_lib.dptr(self.weight), color=_lib.dptr(self.color),
+                                         record=_lib.dptr(record, torch.int64))
+            for d in range(3):
+                a.ticks[d] = _lib.dptr(self._ticks_dev[d], torch.float64)
+            _lib.check(_lib.lib().mipsf_deintegrate_views(C.byref(a), _lib.stream_ptr()), "deintegrate_views")
+        return record
+
+    def reintegrate_enqueue(self, depth: torch.Tensor, poses_old: torch.Tensor, poses_new: torch.Tensor, K,
+                            rgb: Optional[torch.Tensor] = None, depth_max: float = math.inf, records=None, flags: int = 0):
+        """deintegrate_enqueue at ``poses_old``, then integrate_enqueue at ``poses_new``, of every view given: two launches on the
+        current stream, no selection and nothing read back, for use inside a captured sequence.  Device tensors as for
+        integrate_enqueue; ``records`` (int64 [4], int64 [2]) keeps the two records in place -> (remove record, fuse record)"""
+        self._removable()
+        if tuple(poses_new.shape) != tuple(poses_old.shape):
+            raise ValueError(f"poses: {tuple(poses_old.shape)} old and {tuple(poses_new.shape)} new")
+        gone, fused = (None, None) if records is None else records
+        gone = self.deintegrate_enqueue(depth, poses_old, K, rgb, depth_max, gone, flags)
+        fused = self.integrate_enqueue(depth, poses_new, K, rgb, depth_max, fused, flags)
+        return gone, fused
 
     def sample_enqueue(self, points: torch.Tensor) -> torch.Tensor:
         """points float64 [m,3] in index units on the device -> colour fp32 [m,3] on the device (mipsf_tsdf_sample)"""
@@ -320,6 +399,70 @@ class TSDFVolume:
                        for k in range(0, max(n, 1), per)]
             got = torch.stack(records).cpu().numpy()
         return TSDFCounts(int(got[:, 0].sum()), int(got[-1, 1]))
+
+    def deintegrate(self, depth, c2w, K, rgb=None, depth_max: float = math.inf, views_per_call: Optional[int] = None) -> RemoveCounts:
+        """Takes the views out of the volume again, in the order given: the inverse of ``integrate`` for views that were fused with
+        these very images, poses, K and depth_max (the pairs of a view are found by projecting again), in a volume made without
+        ``max_weight``.  The same forms of arguments as ``integrate``; the cut into calls does not reach the bytes.  What remains is
+        the mean of the remaining views up to the rounding of the steps; with every view removed, the all-zero
+        state exactly.  A pose with a NaN removes nothing, as it fused nothing.  ``missing`` counts pairs that found no weight to
+        take from: a sign that a view was not in the volume, not a proof that the others were.  One read-back of 32 bytes a call."""
+        self._removable()
+        with torch.cuda.device(self.device):
+            D = _images(depth, self.device, 0, "depth")
+            P = _poses(c2w, self.device)
+            C3 = None if rgb is None else _images(rgb, self.device, 3, "rgb")
+            n = D.shape[0]
+            if P.shape[0] != n:
+                raise ValueError(f"{n} depth images and {P.shape[0]} poses")
+            per = max(n, 1) if views_per_call is None else int(views_per_call)
+            if per < 1:
+                raise ValueError("views_per_call must be positive")
+            records = [self.deintegrate_enqueue(D[k:k + per], P[k:k + per], K, None if C3 is None else C3[k:k + per], depth_max)
+                       for k in range(0, max(n, 1), per)]
+            got = torch.stack(records).cpu().numpy()
+        return RemoveCounts(int(got[:, 0].sum()), int(got[:, 1].sum()), int(got[:, 2].sum()), int(got[-1, 3]))
+
+    def reintegrate(self, depth, c2w_old, c2w_new, K, rgb=None, depth_max: float = math.inf, min_translation: float = 0.0,
+                    min_rotation: float = 0.0) -> ReintegrateCounts:
+        """Moves fused views to new poses: the views whose pose moved are removed at ``c2w_old``, in ascending order, and then fused
+        at ``c2w_new``, in ascending order -- two launches on one stream and one read-back, paid for the moved views only.  The
+        step after a loop closure:
+
+            poses_new = pose_graph.rebase(poses_world, submap_of_pose, anchors_old, anchors_new)
+            vol.reintegrate(depth, poses_world, poses_new, K)
+
+        ``depth``, ``rgb``, ``c2w_old``, K and depth_max are what the views were fused with (see ``deintegrate``).  Which views
+        moved is decided on the host in float64, on the fp32 poses the kernels take (poses that lie on the device are copied over,
+        64 bytes a view): a view moved when its translation changed by more than ``min_translation`` metres or its rotation by
+        more than ``min_rotation`` radians; with both at 0, when any word of its pose differs.  With a threshold given, equal
+        poses never count as moved, and a pose that is not finite (a lost frame) counts as moved when the other one is finite:
+        its view is then fused, or removed, for the first time.  ``rebase`` moves the poses of a sub-map whose anchor stayed by
+        a rounding (a few 1e-7 of their entries): thresholds of 1e-6 and more leave them alone.  Unmoved views are not touched
+        and cost nothing; when no view moved neither kernel is launched and no word changes, and ``observed`` is counted from
+        the weights (one pass over them and a read-back).  The
+        volume then holds the fusion at the new poses up to the rounding of the steps: equal weights, tsdf within 2^-21 on the
+        measured cases."""
+        self._removable()
+        with torch.cuda.device(self.device):
+            D = _images(depth, self.device, 0, "depth")
+            P0, P1 = _poses(c2w_old, self.device), _poses(c2w_new, self.device)
+            C3 = None if rgb is None else _images(rgb, self.device, 3, "rgb")
+            n = D.shape[0]
+            if P0.shape[0] != n or P1.shape[0] != n:
+                raise ValueError(f"{n} depth images, {P0.shape[0]} old poses and {P1.shape[0]} new poses")
+            if (C3 is None) != (self.color is None):
+                raise ValueError("rgb goes with a volume made with color=True, and such a volume needs rgb")
+            moved = np.nonzero(_moved(P0.cpu().numpy(), P1.cpu().numpy(), float(min_translation), float(min_rotation)))[0]
+            if len(moved) == 0:
+                seen = int(torch.count_nonzero(self.weight > 0))
+                return ReintegrateCounts(0, RemoveCounts(0, 0, 0, seen), TSDFCounts(0, seen))
+            if len(moved) < n:
+                pick = torch.from_numpy(moved).to(self.device)
+                D, P0, P1 = D[pick], P0[pick], P1[pick]
+                C3 = None if C3 is None else C3[pick]
+            got = torch.cat(self.reintegrate_enqueue(D, P0, P1, K, C3, depth_max)).cpu().numpy()
+        return ReintegrateCounts(len(moved), RemoveCounts(*(int(x) for x in got[:4])), TSDFCounts(int(got[4]), int(got[5])))
 
     def volume(self, min_weight: float = 1.0) -> torch.Tensor:
         """the marching input: tsdf where weight >= min_weight, -inf (unobserved, off for the marcher) elsewhere"""
