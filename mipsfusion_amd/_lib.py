@@ -460,6 +460,21 @@ SPARSE_SIGNATURES = {
 }
 
 
+# include/mipsf_sparse_remove.h (views taken out of the sparse volume again; the per-brick history that tells which views a brick holds)
+SPARSE_UNBORN, SPARSE_MAX_VIEW_ID = 0xFFFFFFFF, 0xFFFFFFFE
+SPARSE_REMOVE_RECORD_WORDS = 5             # uint64 removed, missing, emptied, observed, bricks_emptied
+SparseStampArgs = _args("SparseStampArgs", [("n", _CU), ("vol", SparseVolume), ("born", _VP), ("serial", _VP)])
+SparseDeintegrateArgs = _args("SparseDeintegrateArgs", [("n", _CU), ("H", _CU), ("W", _CU), ("flags", _CU), ("reserved", _CU),
+                                                        ("fx", C.c_double), ("fy", C.c_double), ("cx", C.c_double), ("cy", C.c_double),
+                                                        ("trunc", C.c_double), ("depth_max", C.c_double),
+                                                        ("vol", SparseVolume), ("depth", _VP), ("rgb", _VP), ("poses", _VP), ("view_ids", _VP),
+                                                        ("born", _VP), ("record", _VP)])
+SPARSE_REMOVE_SIGNATURES = {
+    "mipsf_sparse_stamp": (_I, [C.POINTER(SparseStampArgs), _P]),
+    "mipsf_sparse_deintegrate": (_I, [C.POINTER(SparseDeintegrateArgs), _P]),
+}
+
+
 # include/mipsf_sparse_mesh.h (the mesh of the sparse volume marched brick by brick; the colour of its vertices)
 SPARSE_MESH_MAX_SIDE, SPARSE_MESH_SCAN_TILE = 21474, 1024
 SPARSE_MESH_MAX_TRIS = 0x0FFFFFFF          # what the weld table of mipsf_mcubes_weld holds
@@ -564,7 +579,8 @@ def lib() -> C.CDLL:
                                        + list(RASTER_SIGNATURES.items()) + list(TSDF_SIGNATURES.items())
                                        + list(IMAGE_SIGNATURES.items()) + list(TRACK_SIGNATURES.items()) + list(TRACK_COLOR_SIGNATURES.items())
                                        + list(SHADE_SIGNATURES.items()) + list(SPARSE_SIGNATURES.items())
-                                       + list(SPARSE_MESH_SIGNATURES.items()) + list(DEINTEGRATE_SIGNATURES.items())):
+                                       + list(SPARSE_MESH_SIGNATURES.items()) + list(DEINTEGRATE_SIGNATURES.items())
+                                       + list(SPARSE_REMOVE_SIGNATURES.items())):
             fn = getattr(handle, name)
             fn.restype = res
             fn.argtypes = args

@@ -508,18 +508,10 @@ MIPSF_SINGLE_FP32 __global__ void __launch_bounds__(TPB) sparse_raycast_kernel(P
     if (tid == 0 && hits) atomicAdd((unsigned long long*)&record->hits, (unsigned long long)hits);
 }
 
-// ------------------------------------------------------------------------------------------------ host
-int images_ok(uint32_t n, uint32_t H, uint32_t W, double fx, double fy, double cx, double cy, const char* who) {
-    MIPSF_REQUIRE(n == 0 || (H > 0 && W > 0), "%s: an image of %u x %u has no pixels", who, H, W);
-    MIPSF_REQUIRE(H <= MIPSF_TSDF_MAX_SIDE && W <= MIPSF_TSDF_MAX_SIDE, "%s: image %u x %u, at most %u a side", who, H, W, MIPSF_TSDF_MAX_SIDE);
-    MIPSF_REQUIRE(n <= MIPSF_SPARSE_MAX_VIEWS, "%s: %u views, at most %u a call", who, n, MIPSF_SPARSE_MAX_VIEWS);
-    MIPSF_REQUIRE(pos_finite(fx) && pos_finite(fy) && is_finite(cx) && is_finite(cy), "%s: intrinsics %g %g %g %g", who, fx, fy, cx, cy);
-    return 0;
-}
-
 }  // namespace
 }  // namespace mipsf
 
+// ------------------------------------------------------------------------------------------------ host
 using namespace mipsf;
 
 extern "C" uint64_t mipsf_sparse_scan_words(uint32_t X, uint32_t Y, uint32_t Z) {

@@ -1,7 +1,7 @@
 // The brick-sparse volume as the kernels read it (include/mipsf_sparse.h), stated once for sparse.hip, which fuses, gathers and ray
-// casts it, and sparse_mesh.hip, which marches it brick by brick: the volume by value, voxel -> word of the pool through the table,
-// the colour of a point (the rule of mipsf_tsdf_sample with the corner reads through the table), and what every entry point refuses
-// of a volume.
+// casts it, sparse_mesh.hip, which marches it brick by brick, and sparse_remove.hip, which takes views out of it again: the volume by
+// value, voxel -> word of the pool through the table, the colour of a point (the rule of mipsf_tsdf_sample with the corner reads
+// through the table), and what every entry point refuses of a volume and of the views.
 #pragma once
 #include <math.h>
 
@@ -83,6 +83,15 @@ inline int volume_ok(const mipsf_sparse_volume& g, const char* who) {
                   g.origin[2]);
     MIPSF_REQUIRE(g.ticks[0] && g.ticks[1] && g.ticks[2] && g.table && g.slot_brick && g.birth && g.count && g.tsdf && g.weight,
                   "%s: null pointer in the volume", who);
+    return 0;
+}
+
+// what the entry points that take views refuse of the images and the intrinsics; 0: fine
+inline int images_ok(uint32_t n, uint32_t H, uint32_t W, double fx, double fy, double cx, double cy, const char* who) {
+    MIPSF_REQUIRE(n == 0 || (H > 0 && W > 0), "%s: an image of %u x %u has no pixels", who, H, W);
+    MIPSF_REQUIRE(H <= MIPSF_TSDF_MAX_SIDE && W <= MIPSF_TSDF_MAX_SIDE, "%s: image %u x %u, at most %u a side", who, H, W, MIPSF_TSDF_MAX_SIDE);
+    MIPSF_REQUIRE(n <= MIPSF_SPARSE_MAX_VIEWS, "%s: %u views, at most %u a call", who, n, MIPSF_SPARSE_MAX_VIEWS);
+    MIPSF_REQUIRE(pos_finite(fx) && pos_finite(fy) && is_finite(cx) && is_finite(cy), "%s: intrinsics %g %g %g %g", who, fx, fy, cx, cy);
     return 0;
 }
 

@@ -2,7 +2,8 @@
 // colours marched vertices with it, and tsdf_track.hip, which colours the hits of a ray cast; and what a view does to a voxel of the
 // dense volume -- the views and the volume by value, the brick's ball and its test against a view, the projection and `updated` of
 // mipsf_tsdf_integrate -- stated once for tsdf.hip, which adds the view to the running mean, and tsdf_remove.hip, which takes it out
-// again (include/mipsf_deintegrate.h).  Device code only.
+// again (include/mipsf_deintegrate.h); and the step that takes it out, stated once for tsdf_remove.hip and sparse_remove.hip, which
+// takes views out of the brick-sparse volume (include/mipsf_sparse_remove.h).  Device code only.
 #pragma once
 #include "common.h"
 #include "../../include/mipsf_tsdf.h"
@@ -119,6 +120,32 @@ __device__ __forceinline__ bool tsdf_view_hits(const TsdfFrames& s, const TsdfVi
     val = sdf / s.trunc;
     if (val > 1.0) val = 1.0;
     return true;
+}
+
+// What a view that hits a voxel does to its running words when it is taken out again (the rule of include/mipsf_deintegrate.h):
+// stated once for tsdf_remove.hip and sparse_remove.hip.  val is tsdf_view_hits's; C the view's colour at the pixel (COLOR only).
+template <bool COLOR>
+__device__ __forceinline__ void tsdf_remove_step(float& tsdf, float& weight, float* color, double val, const float* __restrict__ C, uint64_t& removed,
+                                                 uint64_t& missing, uint64_t& emptied) {
+    const double w0 = (double)weight;
+    if (!(w0 > 0.0)) {                                                          // nothing of this view is in the voxel (a NaN weight too)
+        ++missing;
+        return;
+    }
+    ++removed;
+    const double w1 = w0 - 1.0;
+    if (!(w1 > 0.0)) {                                                          // the last view leaves: the never-observed state
+        tsdf = 0.0f, weight = 0.0f;
+        if (COLOR) color[0] = color[1] = color[2] = 0.0f;
+        ++emptied;
+        return;
+    }
+    tsdf = (float)((((double)tsdf) * w0 - val) / w1);
+    if (COLOR) {
+#pragma unroll
+        for (int ch = 0; ch < 3; ++ch) color[ch] = (float)((((double)color[ch]) * w0 - (double)C[ch]) / w1);
+    }
+    weight = (float)w1;
 }
 
 // ------------------------------------------------------------------------------------------------ the colour of a point

@@ -7,7 +7,8 @@
 // one lane per view tests the brick's ball, the survivors go to LDS in ascending order and every lane walks that list.  What a
 // view does to a voxel -- the ball test, the projection, `updated` -- is tsdf_dev.h's, the same code the fusion runs, so a view
 // is taken out of exactly the voxels it went into; only the step on the running words differs: a subtraction for the addition,
-// w0 - 1 for w0 + 1, and the never-observed state, without a division, when the last view leaves.
+// w0 - 1 for w0 + 1, and the never-observed state, without a division, when the last view leaves (tsdf_remove_step, tsdf_dev.h: the
+// sparse volume's removal, sparse_remove.hip, runs the same).
 #include "block_dev.h"
 #include "tsdf_dev.h"
 #include "../../include/mipsf_deintegrate.h"
@@ -91,26 +92,8 @@ MIPSF_SINGLE_FP32 __global__ void __launch_bounds__(TPB) tsdf_remove_kernel(Tsdf
                 size_t pixel;
                 double val;
                 if (!(ok[r] && tsdf_view_hits(s, row, D, pz[r], pixel, val))) continue;
-                const double w0 = (double)weight[r];
-                if (!(w0 > 0.0)) {                                              // nothing of this view is in the voxel (a NaN weight too)
-                    ++missing;
-                    continue;
-                }
-                ++removed;
-                const double w1 = w0 - 1.0;
-                if (!(w1 > 0.0)) {                                              // the last view leaves: the never-observed state
-                    tsdf[r] = 0.0f, weight[r] = 0.0f;
-                    if (COLOR) color[r * 3] = color[r * 3 + 1] = color[r * 3 + 2] = 0.0f;
-                    ++emptied;
-                    continue;
-                }
-                tsdf[r] = (float)((((double)tsdf[r]) * w0 - val) / w1);
-                if (COLOR) {
-                    const float* C = s.rgb + ((size_t)view * hw + pixel) * 3;
-#pragma unroll
-                    for (int ch = 0; ch < 3; ++ch) color[r * 3 + ch] = (float)((((double)color[r * 3 + ch]) * w0 - (double)C[ch]) / w1);
-                }
-                weight[r] = (float)w1;
+                tsdf_remove_step<COLOR>(tsdf[r], weight[r], color + (COLOR ? r * 3 : 0), val, COLOR ? s.rgb + ((size_t)view * hw + pixel) * 3 : nullptr,
+                                        removed, missing, emptied);
             }
         }
     }

@@ -4,7 +4,9 @@ a slot when a depth pixel of a fused view lands within ``band`` of it; only allo
 kernels are those of ``csrc/sparse.hip`` (C ABI: include/mipsf_sparse.h):
 
     SparseTSDFVolume               the state (index grid, pool of tsdf, weight, optionally colour; all on the device) and integrate /
-                                   to_dense / extract_mesh / extract_mesh_bricks / raycast / track / reset
+                                   to_dense / extract_mesh / extract_mesh_bricks / raycast / track / reset; with ``history=True``
+                                   also deintegrate / reintegrate, which take fused views out again and fuse them at new poses
+                                   (``csrc/sparse_remove.hip``, include/mipsf_sparse_remove.h)
     sparse_tsdf_mesh_from_frames   depth frames + poses -> mesh.Mesh, the namesake of tsdf_mesh_from_frames
     sparse_tsdf_odometry           depth frames -> poses, the namesake of tsdf_odometry
 
@@ -27,7 +29,7 @@ from . import _lib
 from .mesh import Mesh, filter_faces, save_ply
 from .mesh_render import _poses
 from .scene_mesh import _intrinsics
-from .tsdf import Raycast, TSDFVolume, _device, _images, frames_bounds
+from .tsdf import Raycast, TSDFVolume, _device, _images, _moved_views, frames_bounds
 
 BRICK = _lib.TSDF_BRICK
 
@@ -41,14 +43,31 @@ class SparseTSDFCounts(NamedTuple):
     bricks_in_use: int               # slots in use afterwards
 
 
+class SparseRemoveCounts(NamedTuple):
+    removed: int                     # (voxel, view) pairs taken out, over the calls of one deintegrate()
+    missing: int                     # pairs the views hit whose voxel had no positive weight left (a diagnostic, not a guarantee)
+    emptied: int                     # removals that brought a voxel back to the never-observed state
+    observed: int                    # voxels whose weight is positive afterwards
+    bricks_emptied: int              # slots in use without such a voxel afterwards (nothing is freed)
+
+
+class SparseReintegrateCounts(NamedTuple):
+    views_moved: int                 # views removed at their old pose and fused at their new one
+    removed: SparseRemoveCounts
+    fused: SparseTSDFCounts
+    view_ids: np.ndarray             # int64 [n]: the ids the views have now, new for the moved ones
+
+
 class SparseTSDFVolume:
     """A brick-sparse TSDF volume on the device.  Voxel (i,j,k) of the virtual grid ``dims`` sits at origin + voxel_size * (i,j,k);
     ``trunc``, ``max_weight`` and the words are those of TSDFVolume.  ``capacity_bricks`` slots of 1024 voxels are allocated at once
     (8 KB a slot, 20 KB with colour); ``band`` (trunc by default) is how far in front of and behind a depth pixel bricks are
-    allocated."""
+    allocated.  With ``history`` the volume also keeps, per slot, the id of the first view the slot took (``born``; the id of a
+    view is the count of views handed to integrate_enqueue before it, ``views_fused`` on the host and ``serial`` on the device), which
+    is what ``deintegrate`` and ``reintegrate`` need; without it nothing of the volume or its launches changes."""
 
     def __init__(self, origin, voxel_size: float, dims, trunc: float, capacity_bricks: int, color: bool = False, max_weight: float = math.inf,
-                 band: Optional[float] = None, device=None):
+                 band: Optional[float] = None, device=None, history: bool = False):
         self.origin = np.asarray(origin, np.float64).reshape(3).copy()
         self.voxel_size, self.trunc, self.max_weight = float(voxel_size), float(trunc), float(max_weight)
         self.band = self.trunc if band is None else float(band)
@@ -69,6 +88,8 @@ class SparseTSDFVolume:
         self.steps = int(math.ceil(self.band / self.voxel_size))
         self.device = _device(device)
         self.ticks = tuple(self.origin[a] + self.voxel_size * np.arange(self.dims[a], dtype=np.float64) for a in range(3))
+        self.history, self.views_fused, self.last_view_ids = bool(history), 0, np.zeros(0, np.int64)
+        self.born = self.serial = None
         lib = _lib.lib()
         with torch.cuda.device(self.device):
             dev = self.device
@@ -82,6 +103,9 @@ class SparseTSDFVolume:
             self._birth = torch.zeros(self.capacity, dtype=torch.int32, device=dev)
             self._mark = torch.empty(self.bricks, dtype=torch.int32, device=dev)
             self._scan = torch.empty(int(lib.mipsf_sparse_scan_words(*self.dims)), dtype=torch.int32, device=dev)
+            if self.history:                 # uint32 words: -1 is MIPSF_SPARSE_UNBORN
+                self.born = torch.full((self.capacity,), -1, dtype=torch.int32, device=dev)
+                self.serial = torch.zeros(1, dtype=torch.int32, device=dev)
         self._bind()
 
     def _bind(self) -> None:
@@ -103,6 +127,17 @@ class SparseTSDFVolume:
         for t in (self.tsdf, self.weight, self.color):
             if t is not None:
                 t.zero_()
+        if self.history:
+            self.born.fill_(-1)
+            self.serial.zero_()
+        self.views_fused, self.last_view_ids = 0, np.zeros(0, np.int64)
+
+    def sync_views(self) -> int:
+        """Reads the device's count of fused views into ``views_fused`` (one read-back of 4 bytes): for callers that replay a captured
+        integrate_enqueue, which moves the device's word and not the host's -> views_fused"""
+        self._historied()
+        self.views_fused = int(self.serial.item()) & 0xFFFFFFFF
+        return self.views_fused
 
     # ----------------------------------------------------------------------------------------------------------- enqueue only
     def _views(self, depth, poses, rgb):
@@ -150,8 +185,71 @@ class SparseTSDFVolume:
         [n,H,W,3] or None, all on the device -> (record int64 [2]: pairs updated, voxels observed; record int64 [4]: bricks marked,
         new, dropped, in use), both on the device"""
         self._views(depth, poses, rgb)
+        if not self.history:
+            alloc = self.allocate_enqueue(depth, poses, K, depth_max)
+            return self.fuse_enqueue(depth, poses, K, rgb, depth_max, flags=flags), alloc
+        n = depth.shape[0]
+        if self.views_fused + n > _lib.SPARSE_MAX_VIEW_ID:
+            raise ValueError(f"{n} views after {self.views_fused}: view ids end at {_lib.SPARSE_MAX_VIEW_ID}")
         alloc = self.allocate_enqueue(depth, poses, K, depth_max)
+        self.stamp_enqueue(n)
         return self.fuse_enqueue(depth, poses, K, rgb, depth_max, flags=flags), alloc
+
+    def stamp_enqueue(self, n: int) -> None:
+        """mipsf_sparse_stamp between allocate_enqueue and fuse_enqueue of the same ``n`` views: the slots that take their first view
+        get its id, the device's ``serial`` and the host's ``views_fused`` move on by n, and ``last_view_ids`` holds the ids of the n
+        views; nothing is read back"""
+        self._historied()
+        with torch.cuda.device(self.device):
+            a = _lib.SparseStampArgs.new(n=int(n), vol=self._vol, born=_lib.dptr(self.born, torch.int32), serial=_lib.dptr(self.serial, torch.int32))
+            _lib.check(_lib.lib().mipsf_sparse_stamp(C.byref(a), _lib.stream_ptr()), "sparse_stamp")
+        self.last_view_ids = self.views_fused + np.arange(int(n), dtype=np.int64)
+        self.views_fused += int(n)
+
+    def _historied(self) -> None:
+        if not self.history:
+            raise ValueError("history: the volume was made with history=False and does not know which views a brick holds; make it with history=True")
+
+    def _removable(self) -> None:
+        self._historied()
+        if math.isfinite(self.max_weight):
+            raise ValueError(f"views cannot be removed from a volume made with max_weight {self.max_weight}: a capped running mean is a "
+                             f"moving average, which has no inverse; make the volume with max_weight=inf")
+
+    def deintegrate_enqueue(self, depth: torch.Tensor, poses: torch.Tensor, K, view_ids: torch.Tensor, rgb: Optional[torch.Tensor] = None,
+                            depth_max: float = math.inf, record: Optional[torch.Tensor] = None, flags: int = 0) -> torch.Tensor:
+        """One call of mipsf_sparse_deintegrate, the inverse of integrate_enqueue for views fused with these very arguments under
+        the ids ``view_ids`` (int32 or uint32 [n], the words of the unsigned ids, on the device); nothing is read back and nothing is
+        freed -> record int64 [5] on the device: pairs removed, pairs missing, voxels emptied, voxels with a positive weight, slots in
+        use without one"""
+        self._removable()
+        self._views(depth, poses, rgb)
+        n, H, W = depth.shape
+        if not torch.is_tensor(view_ids) or view_ids.dtype not in (torch.int32, torch.uint32) or tuple(view_ids.shape) != (n,):
+            raise ValueError(f"view_ids: expected an int32 or uint32 tensor [{n}] on the device, got "
+                             f"{(view_ids.dtype, tuple(view_ids.shape)) if torch.is_tensor(view_ids) else type(view_ids).__name__}")
+        fx, fy, cx, cy = (float(x) for x in _intrinsics(K))
+        with torch.cuda.device(self.device):
+            record = torch.empty(_lib.SPARSE_REMOVE_RECORD_WORDS, dtype=torch.int64, device=self.device) if record is None else record
+            a = _lib.SparseDeintegrateArgs.new(n=n, H=H, W=W, flags=int(flags), fx=fx, fy=fy, cx=cx, cy=cy, trunc=self.trunc, depth_max=float(depth_max),
+                                               vol=self._vol, depth=depth.data_ptr() if n else None,
+                                               rgb=None if rgb is None or not n else rgb.data_ptr(), poses=poses.data_ptr() if n else None,
+                                               view_ids=_lib.dptr(view_ids, view_ids.dtype) if n else None,
+                                               born=_lib.dptr(self.born, torch.int32), record=_lib.dptr(record, torch.int64))
+            _lib.check(_lib.lib().mipsf_sparse_deintegrate(C.byref(a), _lib.stream_ptr()), "sparse_deintegrate")
+        return record
+
+    def reintegrate_enqueue(self, depth: torch.Tensor, poses_old: torch.Tensor, poses_new: torch.Tensor, K, view_ids: torch.Tensor,
+                            rgb: Optional[torch.Tensor] = None, depth_max: float = math.inf, flags: int = 0):
+        """deintegrate_enqueue at ``poses_old`` under ``view_ids``, then integrate_enqueue at ``poses_new``, of every view given: no
+        selection and nothing read back.  The views get fresh ids (``last_view_ids``) -> (remove record int64 [5], fuse record
+        int64 [2], allocation record int64 [4]), on the device"""
+        self._removable()
+        if tuple(poses_new.shape) != tuple(poses_old.shape):
+            raise ValueError(f"poses: {tuple(poses_old.shape)} old and {tuple(poses_new.shape)} new")
+        gone = self.deintegrate_enqueue(depth, poses_old, K, view_ids, rgb, depth_max, flags=flags)
+        fused, alloc = self.integrate_enqueue(depth, poses_new, K, rgb, depth_max, flags=flags)
+        return gone, fused, alloc
 
     def gather_enqueue(self, lo, hi) -> TSDFVolume:
         """mipsf_sparse_gather: the window lo <= index < hi as a TSDFVolume; nothing is read back"""
@@ -218,8 +316,88 @@ class SparseTSDFVolume:
             records = [torch.cat(self.integrate_enqueue(D[k:k + per], P[k:k + per], K, None if C3 is None else C3[k:k + per], depth_max))
                        for k in range(0, max(n, 1), per)]
             got = torch.stack(records).cpu().numpy()
+        if self.history:
+            self.last_view_ids = self.views_fused - n + np.arange(n, dtype=np.int64)
         return SparseTSDFCounts(int(got[:, 0].sum()), int(got[-1, 1]), int(got[:, 2].sum()), int(got[:, 3].sum()), int(got[:, 4].sum()),
                                 int(got[-1, 5]))
+
+    def _ids(self, view_ids, n: int) -> np.ndarray:
+        """view ids as the caller has them (a list, an array, a tensor) -> int64 [n] on the host, each the id of a fused view"""
+        ids = np.asarray(view_ids.detach().cpu() if torch.is_tensor(view_ids) else view_ids).reshape(-1)
+        if len(ids) != n or (n and ids.dtype.kind not in "iu"):
+            raise ValueError(f"view_ids: expected {n} integer ids, one a view, got {len(ids)} of type {ids.dtype}")
+        ids = ids.astype(np.int64)
+        if n and (ids.min() < 0 or ids.max() >= self.views_fused):
+            raise ValueError(f"view_ids: ids from {int(ids.min())} to {int(ids.max())}, but the volume has fused views 0 .. {self.views_fused - 1} only")
+        return ids
+
+    def _ids_dev(self, ids: np.ndarray) -> torch.Tensor:
+        return torch.from_numpy(ids.astype(np.uint32).view(np.int32)).to(self.device)
+
+    def deintegrate(self, depth, c2w, K, view_ids, rgb=None, depth_max: float = math.inf, views_per_call: Optional[int] = None) -> SparseRemoveCounts:
+        """Takes the views out of the volume again, in the order given: the inverse of ``integrate`` for views that were fused with
+        these very images, poses, K and depth_max under the ids ``view_ids`` (``last_view_ids`` after their ``integrate``), in a
+        volume made with ``history=True`` and without ``max_weight``.  A brick gives up the views it took -- those with an id from
+        its ``born`` on -- and no others.  The same forms of arguments as ``integrate``; the cut into calls does not reach the bytes.
+        What remains is the mean of the remaining views up to the rounding of the steps; with every view removed,
+        the all-zero words exactly.  Nothing is freed: an emptied brick keeps its slot (``bricks_emptied``).  One read-back."""
+        self._removable()
+        with torch.cuda.device(self.device):
+            D = _images(depth, self.device, 0, "depth")
+            P = _poses(c2w, self.device)
+            C3 = None if rgb is None else _images(rgb, self.device, 3, "rgb")
+            n = D.shape[0]
+            if P.shape[0] != n:
+                raise ValueError(f"{n} depth images and {P.shape[0]} poses")
+            ids = self._ids_dev(self._ids(view_ids, n))
+            per = min(max(n, 1), _lib.SPARSE_MAX_VIEWS) if views_per_call is None else int(views_per_call)
+            if per < 1:
+                raise ValueError("views_per_call must be positive")
+            records = [self.deintegrate_enqueue(D[k:k + per], P[k:k + per], K, ids[k:k + per], None if C3 is None else C3[k:k + per], depth_max)
+                       for k in range(0, max(n, 1), per)]
+            got = torch.stack(records).cpu().numpy()
+        return SparseRemoveCounts(int(got[:, 0].sum()), int(got[:, 1].sum()), int(got[:, 2].sum()), int(got[-1, 3]), int(got[-1, 4]))
+
+    def reintegrate(self, depth, c2w_old, c2w_new, K, view_ids, rgb=None, depth_max: float = math.inf, min_translation: float = 0.0,
+                    min_rotation: float = 0.0) -> SparseReintegrateCounts:
+        """Moves fused views to new poses, as TSDFVolume.reintegrate does and with its selection of the moved views (on the host, in
+        float64: translation above ``min_translation`` or rotation above ``min_rotation``; with both at 0 any differing word): the
+        moved views are removed at ``c2w_old`` under their ``view_ids``, bricks are allocated for them at ``c2w_new`` and they are
+        fused there, under fresh ids.  The step after a loop closure:
+
+            poses_new = pose_graph.rebase(poses_world, submap_of_pose, anchors_old, anchors_new)
+            ids = vol.reintegrate(depth, poses_world, poses_new, K, ids).view_ids
+
+        It costs the moved views only, and one read-back; when no view moved nothing is launched and no word changes (the counts
+        then come from one pass over the weights)."""
+        self._removable()
+        with torch.cuda.device(self.device):
+            D = _images(depth, self.device, 0, "depth")
+            P0, P1 = _poses(c2w_old, self.device), _poses(c2w_new, self.device)
+            C3 = None if rgb is None else _images(rgb, self.device, 3, "rgb")
+            n = D.shape[0]
+            if P0.shape[0] != n or P1.shape[0] != n:
+                raise ValueError(f"{n} depth images, {P0.shape[0]} old poses and {P1.shape[0]} new poses")
+            if (C3 is None) != (self.color is None):
+                raise ValueError("rgb goes with a volume made with color=True, and such a volume needs rgb")
+            ids = self._ids(view_ids, n)
+            moved = _moved_views(P0, P1, min_translation, min_rotation)
+            if len(moved) == 0:
+                live = (self.weight.view(self.capacity, -1) > 0)
+                seen, full, used = (int(x) for x in torch.stack([live.sum(), live.any(1).sum(), self.count[0].to(torch.int64)]).tolist())
+                used = min(used, self.capacity)
+                return SparseReintegrateCounts(0, SparseRemoveCounts(0, 0, 0, seen, used - full), SparseTSDFCounts(0, seen, 0, 0, 0, used), ids)
+            if len(moved) > _lib.SPARSE_MAX_VIEWS:
+                raise ValueError(f"{len(moved)} views moved, at most {_lib.SPARSE_MAX_VIEWS} a call: reintegrate them in parts")
+            if len(moved) < n:
+                pick = torch.from_numpy(moved).to(self.device)
+                D, P0, P1 = D[pick], P0[pick], P1[pick]
+                C3 = None if C3 is None else C3[pick]
+            got = torch.cat(self.reintegrate_enqueue(D, P0, P1, K, self._ids_dev(ids[moved]), C3, depth_max)).cpu().numpy()
+            ids = ids.copy()
+            ids[moved] = self.last_view_ids
+        return SparseReintegrateCounts(len(moved), SparseRemoveCounts(*(int(x) for x in got[:5])),
+                                       SparseTSDFCounts(int(got[5]), int(got[6]), int(got[7]), int(got[8]), int(got[9]), int(got[10])), ids)
 
     def allocated_bricks(self) -> np.ndarray:
         """the bricks in use, in slot order -> int64 [m,3] brick coordinates (one read-back of slot_brick)"""

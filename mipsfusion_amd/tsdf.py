@@ -127,6 +127,12 @@ def _moved(old: np.ndarray, new: np.ndarray, min_translation: float, min_rotatio
         return (fine_a != fine_b) | (fine_a & fine_b & ((shift > min_translation) | (turn > min_rotation)))
 
 
+def _moved_views(poses_old: torch.Tensor, poses_new: torch.Tensor, min_translation: float, min_rotation: float) -> np.ndarray:
+    """fp32 poses [n,4,4] before and after, host or device -> int64 [m]: the views ``_moved`` finds moved, ascending.  The selection
+    of TSDFVolume.reintegrate and SparseTSDFVolume.reintegrate."""
+    return np.nonzero(_moved(poses_old.cpu().numpy(), poses_new.cpu().numpy(), float(min_translation), float(min_rotation)))[0]
+
+
 class TSDFVolume:
     """A dense TSDF volume on the device.  Voxel (i,j,k) sits at origin + voxel_size * (i,j,k) (float64, rounded to fp32 by the
     kernel); ``trunc`` is the truncation distance in metres.  tsdf is in units of trunc: 1 in free space, 0 on the surface,
@@ -453,7 +459,7 @@ class TSDFVolume:
                 raise ValueError(f"{n} depth images, {P0.shape[0]} old poses and {P1.shape[0]} new poses")
             if (C3 is None) != (self.color is None):
                 raise ValueError("rgb goes with a volume made with color=True, and such a volume needs rgb")
-            moved = np.nonzero(_moved(P0.cpu().numpy(), P1.cpu().numpy(), float(min_translation), float(min_rotation)))[0]
+            moved = _moved_views(P0, P1, min_translation, min_rotation)
             if len(moved) == 0:
                 seen = int(torch.count_nonzero(self.weight > 0))
                 return ReintegrateCounts(0, RemoveCounts(0, 0, 0, seen), TSDFCounts(0, seen))

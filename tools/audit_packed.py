@@ -14,7 +14,7 @@ import tempfile
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 SRC = os.path.join(ROOT, "mipsfusion_amd", "csrc")
-UNITS = ("capi", "hashgrid", "elementwise", "render", "decoder", "decoder16", "wgrad16", "pose", "ro", "mcubes", "fuse", "icp", "posegraph", "submap", "eval", "raster", "shade", "sparse_mesh", "tsdf_remove")
+UNITS = ("capi", "hashgrid", "elementwise", "render", "decoder", "decoder16", "wgrad16", "pose", "ro", "mcubes", "fuse", "icp", "posegraph", "submap", "eval", "raster", "shade", "sparse_mesh", "tsdf_remove", "sparse_remove")
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=off", "-munsafe-fp-atomics", "-w", "-I" + os.path.join(ROOT, "include")]
 
 
