@@ -39,27 +39,31 @@ def mean_masked_sdf(run_network, world, target_d, trunc):
     return torch.mean(valid * sdf.abs(), -1)
 
 
-def swarm_update(mms, pst7, rot, trans, c2):
+def swarm_update(mms, pst7, rot, trans, c2, fit=None, better=None, consts=(0.00001, 1e-5, 0.0001)):
     """RandomOptimizer.py:196-224: advanced-particle weights, weighted mean transform, pose and search-size update.
-    -> rot, trans, search [1,6], info dict."""
-    fit = mms * SDF_WEIGHT
+    -> rot, trans, search [1,6], info dict.
+
+    The keywords are for a float64 evaluation of what an fp32 run decides (tests/tracker_cpu.py): ``fit`` the fitness
+    values as a tensor of its own (a leaf to differentiate by), ``better`` the advanced set as the fp32 comparison took
+    it, ``consts`` the three literals as the values their fp32 forms hold.  Left out, this is the reference's text."""
+    fit = mms * SDF_WEIGHT if fit is None else fit
     f0 = fit[0]
-    better = (fit < f0).to(fit.dtype)
+    better = (fit < f0 if better is None else better).to(fit.dtype)
     w = (f0 - fit) * better
-    wsum = w.sum() + 0.00001
+    wsum = w.sum() + consts[0]
     ok = bool(torch.count_nonzero(better) > 0)
     if ok:
         mean_sdf = (w * mms).sum() / wsum
         mt = (pst7 * w[:, None]).sum(0) / wsum
-        quat = mt[:4] / (mt[:4].norm() + 1e-5)
+        quat = mt[:4] / (mt[:4].norm() + consts[1])
         mt = torch.cat([quat, mt[4:]])
         rot = rot @ p3d_cpu.quaternion_to_matrix(mt[:4])
         trans = trans + mt[4:, None]
     else:
         mean_sdf = mms[0]
         mt = torch.tensor([1.0, 0, 0, 0, 0, 0, 0], dtype=mms.dtype)
-    s = mt[1:].abs() + 0.0001
-    search = (c2 * mean_sdf * s / s.norm() + 0.0001)[None]
+    s = mt[1:].abs() + consts[2]
+    search = (c2 * mean_sdf * s / s.norm() + consts[2])[None]
     if not ok:
         search = search * 2
     return rot, trans, search, {"success": ok, "mean_sdf": mean_sdf, "fitness0": f0, "mean_transform": mt}
