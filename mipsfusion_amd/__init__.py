@@ -19,7 +19,7 @@ _MESH_RENDER = ("render_mesh_depth", "depth_l1", "visible_points", "DepthMetrics
                 "MeshRender", "MeshRenderMetrics")
 _TSDF = ("TSDFVolume", "TSDFCounts", "tsdf_mesh_from_frames", "mesh_from_rendered_depth", "Raycast", "TrackResult", "tsdf_odometry",
          "ColorTrackResult", "RemoveCounts", "ReintegrateCounts")
-_SPARSE_TSDF = ("SparseTSDFVolume", "SparseTSDFCounts", "SparseRemoveCounts", "SparseReintegrateCounts", "sparse_tsdf_mesh_from_frames", "sparse_tsdf_odometry")
+_SPARSE_TSDF = ("SparseTSDFVolume", "SparseTSDFCounts", "SparseRemoveCounts", "SparseReintegrateCounts", "ReleaseCounts", "RestoreCounts", "BrickArchive", "sparse_tsdf_mesh_from_frames", "sparse_tsdf_odometry")
 # (the function image_metrics.image_metrics is reached through its module: the package attribute of that name IS the module)
 _IMAGE_METRICS = ("psnr", "ssim", "ms_ssim", "render_metrics", "gaussian_window", "ImageMetrics", "RenderMetrics")
 _TRAJECTORY = ("align_trajectory", "trajectory_metrics", "TrajectoryMetrics")

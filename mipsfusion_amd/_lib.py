@@ -475,6 +475,24 @@ SPARSE_REMOVE_SIGNATURES = {
 }
 
 
+# include/mipsf_sparse_release.h (slots of the sparse volume given back, archived and restored)
+SPARSE_RELEASE_OUTSIDE, SPARSE_RELEASE_EMPTY, SPARSE_RELEASE_ARCHIVE = 1, 2, 4
+SPARSE_RESTORE_SCRATCH_WORDS = 16
+SPARSE_RELEASE_RECORD_WORDS = 7            # uint64 candidates, released, released_outside, released_empty, deferred, moved, in_use
+SPARSE_RESTORE_RECORD_WORDS = 7            # uint64 listed, invalid, duplicates, occupied, restored, dropped, in_use
+SparseReleaseArgs = _args("SparseReleaseArgs", [("flags", _CU), ("archive_capacity", _CU), ("reserved", _CU), ("vol", SparseVolume), ("born", _VP),
+                                                ("box", _VP), ("arch_brick", _VP), ("arch_born", _VP), ("arch_tsdf", _VP), ("arch_weight", _VP),
+                                                ("arch_color", _VP), ("scratch", _VP), ("record", _VP)])
+SparseRestoreArgs = _args("SparseRestoreArgs", [("m", _CU), ("vol", SparseVolume), ("born", _VP), ("arch_brick", _VP), ("arch_born", _VP),
+                                                ("arch_tsdf", _VP), ("arch_weight", _VP), ("arch_color", _VP), ("mark", _VP), ("scan", _VP),
+                                                ("scratch", _VP), ("record", _VP)])
+SPARSE_RELEASE_SIGNATURES = {
+    "mipsf_sparse_release_scratch_words": (_U64, [_U32]),
+    "mipsf_sparse_release": (_I, [C.POINTER(SparseReleaseArgs), _P]),
+    "mipsf_sparse_restore": (_I, [C.POINTER(SparseRestoreArgs), _P]),
+}
+
+
 # include/mipsf_sparse_mesh.h (the mesh of the sparse volume marched brick by brick; the colour of its vertices)
 SPARSE_MESH_MAX_SIDE, SPARSE_MESH_SCAN_TILE = 21474, 1024
 SPARSE_MESH_MAX_TRIS = 0x0FFFFFFF          # what the weld table of mipsf_mcubes_weld holds
@@ -580,7 +598,7 @@ def lib() -> C.CDLL:
                                        + list(IMAGE_SIGNATURES.items()) + list(TRACK_SIGNATURES.items()) + list(TRACK_COLOR_SIGNATURES.items())
                                        + list(SHADE_SIGNATURES.items()) + list(SPARSE_SIGNATURES.items())
                                        + list(SPARSE_MESH_SIGNATURES.items()) + list(DEINTEGRATE_SIGNATURES.items())
-                                       + list(SPARSE_REMOVE_SIGNATURES.items())):
+                                       + list(SPARSE_REMOVE_SIGNATURES.items()) + list(SPARSE_RELEASE_SIGNATURES.items())):
             fn = getattr(handle, name)
             fn.restype = res
             fn.argtypes = args

@@ -514,6 +514,23 @@ MIPSF_SINGLE_FP32 __global__ void __launch_bounds__(TPB) sparse_raycast_kernel(P
 // ------------------------------------------------------------------------------------------------ host
 using namespace mipsf;
 
+// the allocation around its marks (sparse_dev.h): what mipsf_sparse_allocate launches before and after its mark kernel, for
+// sparse_release.hip, whose restore makes the marks from an archive's bricks
+void mipsf::sparse_fill(void* p, uint64_t words, uint32_t value, hipStream_t st) { fill(p, words, value, st); }
+
+void mipsf::sparse_marks_clear(const Pool& v, uint32_t* mark, mipsf_sparse_alloc_record* record, hipStream_t st) {
+    fill(record, sizeof(mipsf_sparse_alloc_record) / sizeof(uint32_t), 0u, st);
+    fill(mark, v.bricks, UNMARKED, st);
+    fill(v.birth, v.capacity, 0u, st);
+}
+
+void mipsf::sparse_marks_assign(const Pool& v, const uint32_t* mark, uint32_t* scan, mipsf_sparse_alloc_record* record, hipStream_t st) {
+    const uint32_t nb = blocks_for(v.bricks, MIPSF_SPARSE_SCAN_TILE);
+    hipLaunchKernelGGL(sparse_tile_kernel, dim3(nb), dim3(TPB), 0, st, v, mark, scan, record);
+    hipLaunchKernelGGL(sparse_top_kernel, dim3(1), dim3(TPB), 0, st, v, scan, nb, record);
+    hipLaunchKernelGGL(sparse_assign_kernel, dim3(nb), dim3(TPB), 0, st, v, mark, (const uint32_t*)scan, nb);
+}
+
 extern "C" uint64_t mipsf_sparse_scan_words(uint32_t X, uint32_t Y, uint32_t Z) {
     if (X == 0 || Y == 0 || Z == 0) return 0;
     const uint64_t xy = (uint64_t)blocks_for(X, BX) * blocks_for(Y, BY);
@@ -530,17 +547,12 @@ extern "C" int mipsf_sparse_allocate(const mipsf_sparse_allocate_args* a, void* 
     MIPSF_REQUIRE(a->mark && a->scan && a->record && (a->n == 0 || (a->depth && a->poses)), "mipsf_sparse_allocate: null pointer");
     hipStream_t st = (hipStream_t)stream;
     const Pool v = pool_of(a->vol);
-    const uint32_t nb = blocks_for(v.bricks, MIPSF_SPARSE_SCAN_TILE);
-    fill(a->record, sizeof(mipsf_sparse_alloc_record) / sizeof(uint32_t), 0u, st);
-    fill(a->mark, v.bricks, UNMARKED, st);
-    fill(v.birth, v.capacity, 0u, st);
+    sparse_marks_clear(v, a->mark, a->record, st);
     if (a->n > 0) {
         const Views s = {a->depth, a->poses, a->n, a->H, a->W, a->steps, a->fx, a->fy, a->cx, a->cy, a->depth_max};
         hipLaunchKernelGGL(sparse_mark_kernel, dim3(blocks_for((uint64_t)a->H * a->W, TPB), a->n), dim3(TPB), 0, st, v, s, a->mark);
     }
-    hipLaunchKernelGGL(sparse_tile_kernel, dim3(nb), dim3(TPB), 0, st, v, (const uint32_t*)a->mark, a->scan, a->record);
-    hipLaunchKernelGGL(sparse_top_kernel, dim3(1), dim3(TPB), 0, st, v, a->scan, nb, a->record);
-    hipLaunchKernelGGL(sparse_assign_kernel, dim3(nb), dim3(TPB), 0, st, v, (const uint32_t*)a->mark, (const uint32_t*)a->scan, nb);
+    sparse_marks_assign(v, a->mark, a->scan, a->record, st);
     return check_launch("sparse_allocate");
 }
 

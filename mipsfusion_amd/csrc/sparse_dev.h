@@ -1,5 +1,6 @@
 // The brick-sparse volume as the kernels read it (include/mipsf_sparse.h), stated once for sparse.hip, which fuses, gathers and ray
-// casts it, sparse_mesh.hip, which marches it brick by brick, and sparse_remove.hip, which takes views out of it again: the volume by
+// casts it, sparse_mesh.hip, which marches it brick by brick, sparse_remove.hip, which takes views out of it again, and
+// sparse_release.hip, which gives slots back: the volume by
 // value, voxel -> word of the pool through the table, the colour of a point (the rule of mipsf_tsdf_sample with the corner reads
 // through the table), and what every entry point refuses of a volume and of the views.
 #pragma once
@@ -105,5 +106,13 @@ inline Pool pool_of(const mipsf_sparse_volume& g) {
     v.voxel = g.voxel;
     return v;
 }
+
+// sparse.hip: the launches of mipsf_sparse_allocate around its mark kernel, with the kernels as they stand there.  sparse_fill:
+// p[0..words) = value, by a kernel.  sparse_marks_clear: the record 0, every mark 0xffffffff, every birth 0.  sparse_marks_assign: the
+// marked bricks without a slot get the slots count, count + 1, .. in ascending brick index (tile sums, the top block, the tiles
+// again); scan[tiles] keeps the count before.
+void sparse_fill(void* p, uint64_t words, uint32_t value, hipStream_t st);
+void sparse_marks_clear(const Pool& v, uint32_t* mark, mipsf_sparse_alloc_record* record, hipStream_t st);
+void sparse_marks_assign(const Pool& v, const uint32_t* mark, uint32_t* scan, mipsf_sparse_alloc_record* record, hipStream_t st);
 
 }  // namespace mipsf

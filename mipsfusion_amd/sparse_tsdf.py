@@ -14,7 +14,10 @@ Every output is the dense volume's rule read over the dense state with the voxel
 float64 restatement in tests/sparse_cpu.py.  ``extract_mesh`` goes through ``to_dense``: a window of the grid as a TSDFVolume, below
 2^31 voxels a marching call.  ``extract_mesh_bricks`` marches the allocated bricks themselves (csrc/sparse_mesh.hip,
 include/mipsf_sparse_mesh.h): the whole volume in one call whatever the size of the virtual grid, and EQUALS
-tests/sparse_mesh_cpu.py.  Nothing is ever freed.  There is no CPU fallback.
+tests/sparse_mesh_cpu.py.  ``release`` gives slots back -- the bricks outside a box, or the bricks ``deintegrate`` emptied -- closes the
+holes in place and can hand the released bricks to a ``BrickArchive``; ``restore`` brings an archive back (csrc/sparse_release.hip,
+include/mipsf_sparse_release.h), and EQUALS tests/sparse_release_cpu.py.  Until ``release`` is called nothing is
+freed.  There is no CPU fallback.
 """
 from __future__ import annotations
 
@@ -48,7 +51,7 @@ class SparseRemoveCounts(NamedTuple):
     missing: int                     # pairs the views hit whose voxel had no positive weight left (a diagnostic, not a guarantee)
     emptied: int                     # removals that brought a voxel back to the never-observed state
     observed: int                    # voxels whose weight is positive afterwards
-    bricks_emptied: int              # slots in use without such a voxel afterwards (nothing is freed)
+    bricks_emptied: int              # slots in use without such a voxel afterwards (they keep their slots until release(empty=True))
 
 
 class SparseReintegrateCounts(NamedTuple):
@@ -56,6 +59,77 @@ class SparseReintegrateCounts(NamedTuple):
     removed: SparseRemoveCounts
     fused: SparseTSDFCounts
     view_ids: np.ndarray             # int64 [n]: the ids the views have now, new for the moved ones
+
+
+class ReleaseCounts(NamedTuple):
+    candidates: int                  # slots in use for which an enabled predicate held
+    released: int                    # of those, slots given back
+    released_outside: int            # released slots whose brick lay outside the box
+    released_empty: int              # released slots without a voxel of positive weight (a slot may count in both)
+    deferred: int                    # candidates the archive had no room for: they stay in the volume
+    moved: int                       # slots moved to close the holes
+    bricks_in_use: int               # slots in use afterwards
+
+
+class RestoreCounts(NamedTuple):
+    listed: int                      # entries of the archive
+    invalid: int                     # entries whose brick is not a brick of the grid (the unwritten entries of an archive hold -1)
+    duplicates: int                  # valid entries that lost their brick to an entry with a lower index
+    occupied: int                    # bricks listed that have a slot already: they keep their words
+    restored: int                    # bricks that got a slot and their entry's words
+    dropped: int                     # bricks that got none: the pool was full
+    bricks_in_use: int               # slots in use afterwards
+
+
+class BrickArchive:
+    """Bricks taken out of a SparseTSDFVolume by ``release``: per entry the brick (its linear index in the volume's brick grid; -1
+    in an entry nothing was written to), ``born`` when the volume keeps a history, and all the words of the slot.  ``n`` is the count
+    of entries written, None while it has not been read back (``release_enqueue``); the tensors may live on the device or, after
+    ``cpu()``, on the host."""
+
+    def __init__(self, bricks, born, tsdf, weight, color, n=None):
+        self.bricks, self.born, self.tsdf, self.weight, self.color, self.n = bricks, born, tsdf, weight, color, n
+
+    @staticmethod
+    def empty(capacity: int, color: bool, history: bool, device) -> "BrickArchive":
+        capacity = int(capacity)
+        return BrickArchive(torch.full((capacity,), -1, dtype=torch.int32, device=device),
+                            torch.full((capacity,), -1, dtype=torch.int32, device=device) if history else None,
+                            torch.zeros((capacity,) + BRICK, dtype=torch.float32, device=device),
+                            torch.zeros((capacity,) + BRICK, dtype=torch.float32, device=device),
+                            torch.zeros((capacity,) + BRICK + (3,), dtype=torch.float32, device=device) if color else None)
+
+    def __len__(self) -> int:
+        return int(self.bricks.shape[0])
+
+    def _each(self, f, n=None) -> "BrickArchive":
+        return BrickArchive(*(None if t is None else f(t) for t in (self.bricks, self.born, self.tsdf, self.weight, self.color)),
+                            n=self.n if n is None else n)
+
+    def first(self, n: int) -> "BrickArchive":
+        """the first n entries (views of the same storage), as the entries written"""
+        n = int(n)
+        return self._each(lambda t: t[:n], n=n)
+
+    def cpu(self) -> "BrickArchive":
+        return self._each(lambda t: t.cpu())
+
+    def to(self, device) -> "BrickArchive":
+        return self._each(lambda t: t.to(device))
+
+    @staticmethod
+    def cat(archives) -> "BrickArchive":
+        """the entries of several archives in the order given (``restore`` lets the first of two entries of a brick win)"""
+        archives = list(archives)
+        if not archives:
+            raise ValueError("cat: no archives")
+        a0 = archives[0]
+        if any((a.born is None) != (a0.born is None) or (a.color is None) != (a0.color is None) for a in archives):
+            raise ValueError("cat: archives with and without born, or with and without color")
+        known = all(a.n is not None for a in archives)
+        parts = [a.first(a.n) if a.n is not None else a for a in archives]
+        return BrickArchive(*(None if getattr(a0, k) is None else torch.cat([getattr(a, k) for a in parts]) for k in ("bricks", "born", "tsdf", "weight", "color")),
+                            n=sum(a.n for a in archives) if known else None)
 
 
 class SparseTSDFVolume:
@@ -90,6 +164,8 @@ class SparseTSDFVolume:
         self.ticks = tuple(self.origin[a] + self.voxel_size * np.arange(self.dims[a], dtype=np.float64) for a in range(3))
         self.history, self.views_fused, self.last_view_ids = bool(history), 0, np.zeros(0, np.int64)
         self.born = self.serial = None
+        self.bricks_in_use: Optional[int] = 0       # the host's mirror of `count`: what the last read-back saw; None after an enqueue-only call
+        self._release_scratch = None
         lib = _lib.lib()
         with torch.cuda.device(self.device):
             dev = self.device
@@ -130,7 +206,7 @@ class SparseTSDFVolume:
         if self.history:
             self.born.fill_(-1)
             self.serial.zero_()
-        self.views_fused, self.last_view_ids = 0, np.zeros(0, np.int64)
+        self.views_fused, self.last_view_ids, self.bricks_in_use = 0, np.zeros(0, np.int64), 0
 
     def sync_views(self) -> int:
         """Reads the device's count of fused views into ``views_fused`` (one read-back of 4 bytes): for callers that replay a captured
@@ -161,6 +237,7 @@ class SparseTSDFVolume:
                                             vol=self._vol, depth=depth.data_ptr() if n else None, poses=poses.data_ptr() if n else None,
                                             mark=self._mark.data_ptr(), scan=self._scan.data_ptr(), record=_lib.dptr(record, torch.int64))
             _lib.check(_lib.lib().mipsf_sparse_allocate(C.byref(a), _lib.stream_ptr()), "sparse_allocate")
+        self.bricks_in_use = None
         return record
 
     def fuse_enqueue(self, depth: torch.Tensor, poses: torch.Tensor, K, rgb: Optional[torch.Tensor] = None, depth_max: float = math.inf,
@@ -318,6 +395,7 @@ class SparseTSDFVolume:
             got = torch.stack(records).cpu().numpy()
         if self.history:
             self.last_view_ids = self.views_fused - n + np.arange(n, dtype=np.int64)
+        self.bricks_in_use = int(got[-1, 5])
         return SparseTSDFCounts(int(got[:, 0].sum()), int(got[-1, 1]), int(got[:, 2].sum()), int(got[:, 3].sum()), int(got[:, 4].sum()),
                                 int(got[-1, 5]))
 
@@ -340,7 +418,8 @@ class SparseTSDFVolume:
         volume made with ``history=True`` and without ``max_weight``.  A brick gives up the views it took -- those with an id from
         its ``born`` on -- and no others.  The same forms of arguments as ``integrate``; the cut into calls does not reach the bytes.
         What remains is the mean of the remaining views up to the rounding of the steps; with every view removed,
-        the all-zero words exactly.  Nothing is freed: an emptied brick keeps its slot (``bricks_emptied``).  One read-back."""
+        the all-zero words exactly.  Nothing is freed here: an emptied brick keeps its slot (``bricks_emptied``) until
+        ``release(empty=True)`` gives it back.  One read-back."""
         self._removable()
         with torch.cuda.device(self.device):
             D = _images(depth, self.device, 0, "depth")
@@ -396,13 +475,126 @@ class SparseTSDFVolume:
             got = torch.cat(self.reintegrate_enqueue(D, P0, P1, K, self._ids_dev(ids[moved]), C3, depth_max)).cpu().numpy()
             ids = ids.copy()
             ids[moved] = self.last_view_ids
+            self.bricks_in_use = int(got[10])
         return SparseReintegrateCounts(len(moved), SparseRemoveCounts(*(int(x) for x in got[:5])),
                                        SparseTSDFCounts(int(got[5]), int(got[6]), int(got[7]), int(got[8]), int(got[9]), int(got[10])), ids)
+
+    # ----------------------------------------------------------------------------------------------------------- release, restore
+    def release_enqueue(self, box: Optional[torch.Tensor] = None, empty: bool = False, archive_capacity: Optional[int] = None,
+                        record: Optional[torch.Tensor] = None, into: Optional["BrickArchive"] = None):
+        """mipsf_sparse_release; nothing is read back.  ``box``: float64 [6] on the device, lo[3] then hi[3] in world metres: the bricks
+        whose voxel centres all lie outside it are released (a NaN releases nothing); ``empty``: the slots without a voxel of positive
+        weight are.  With ``archive_capacity`` the released bricks go to a BrickArchive of that many entries and no more are released
+        than it holds (``into``: a BrickArchive of the caller's to write to, for a captured graph that is replayed; its entries are the
+        capacity) -> record int64 [7] on the device (ReleaseCounts' fields), or (record, BrickArchive)"""
+        flags = (_lib.SPARSE_RELEASE_OUTSIDE if box is not None else 0) | (_lib.SPARSE_RELEASE_EMPTY if empty else 0)
+        if not flags:
+            raise ValueError("release: give a box, or empty=True, or both")
+        if box is not None and (not torch.is_tensor(box) or box.dtype != torch.float64 or box.numel() != 6):
+            raise ValueError("box: expected a float64 tensor of 6 values on the device, lo[3] then hi[3]")
+        arch = None
+        with torch.cuda.device(self.device):
+            if into is not None:
+                if (into.born is None) != (not self.history) or (into.color is None) != (self.color is None):
+                    raise ValueError("into: the archive's born and color must be there exactly when the volume has history and colour")
+                if archive_capacity is not None and int(archive_capacity) != len(into):
+                    raise ValueError(f"archive_capacity {archive_capacity} with an archive of {len(into)} entries")
+                flags |= _lib.SPARSE_RELEASE_ARCHIVE
+                arch = into
+            elif archive_capacity is not None:
+                if not 0 <= int(archive_capacity) <= _lib.SPARSE_MAX_CAPACITY:
+                    raise ValueError(f"archive_capacity {archive_capacity}: from 0 to {_lib.SPARSE_MAX_CAPACITY}")
+                flags |= _lib.SPARSE_RELEASE_ARCHIVE
+                arch = BrickArchive.empty(int(archive_capacity), self.color is not None, self.history, self.device)
+            if self._release_scratch is None:
+                self._release_scratch = torch.empty(int(_lib.lib().mipsf_sparse_release_scratch_words(self.capacity)) // 2 + 1, dtype=torch.int64,
+                                                    device=self.device)
+            record = torch.empty(_lib.SPARSE_RELEASE_RECORD_WORDS, dtype=torch.int64, device=self.device) if record is None else record
+            some = arch is not None and len(arch) > 0
+            a = _lib.SparseReleaseArgs.new(flags=flags, archive_capacity=len(arch) if arch is not None else 0, vol=self._vol,
+                                           born=_lib.dptr(self.born, torch.int32), box=None if box is None else _lib.dptr(box.contiguous(), torch.float64),
+                                           arch_brick=_lib.dptr(arch.bricks, torch.int32) if some else None,
+                                           arch_born=_lib.dptr(arch.born, torch.int32) if some else None,
+                                           arch_tsdf=_lib.dptr(arch.tsdf) if some else None, arch_weight=_lib.dptr(arch.weight) if some else None,
+                                           arch_color=_lib.dptr(arch.color) if some else None,
+                                           scratch=_lib.dptr(self._release_scratch, torch.int64), record=_lib.dptr(record, torch.int64))
+            _lib.check(_lib.lib().mipsf_sparse_release(C.byref(a), _lib.stream_ptr()), "sparse_release")
+        self.bricks_in_use = None
+        return record if arch is None else (record, arch)
+
+    def _box(self, keep_box) -> torch.Tensor:
+        """a [3,2] array of (lo, hi) per axis, or a tensor of 6 float64 (lo[3], hi[3]) -> float64 [6] on the device"""
+        if torch.is_tensor(keep_box) and keep_box.is_cuda and keep_box.dtype == torch.float64 and keep_box.numel() == 6:
+            return keep_box.reshape(6).contiguous()
+        b = np.asarray(keep_box.detach().cpu() if torch.is_tensor(keep_box) else keep_box, np.float64)
+        if b.shape == (6,):
+            return torch.from_numpy(b.copy()).to(self.device)
+        if b.shape != (3, 2):
+            raise ValueError(f"keep_box: expected [3,2] (lo and hi per axis) or 6 float64 (lo[3], hi[3]), got {b.shape}")
+        return torch.from_numpy(np.concatenate([b[:, 0], b[:, 1]])).to(self.device)
+
+    def release(self, keep_box=None, empty: bool = False, archive: bool = False):
+        """Gives slots back: the bricks that lie wholly outside ``keep_box`` ([3,2] world metres, or a device tensor of 6 float64)
+        and, with ``empty``, the slots ``deintegrate`` left without an observed voxel (its ``bricks_emptied``).  The holes are closed
+        in place, so the slots in use stay 0 .. bricks_in_use - 1 (the numbering of the slots changes, nothing else of the survivors).
+        With ``archive`` the released bricks are returned as a BrickArchive, which ``restore`` takes.  One read-back.
+        -> ReleaseCounts, or (ReleaseCounts, BrickArchive)"""
+        with torch.cuda.device(self.device):
+            box = None if keep_box is None else self._box(keep_box)
+            cap = (self.capacity if self.bricks_in_use is None else self.bricks_in_use) if archive else None
+            got = self.release_enqueue(box, empty, cap)
+            rec, arch = got if archive else (got, None)
+            counts = ReleaseCounts(*(int(x) for x in rec.tolist()))
+        self.bricks_in_use = counts.bricks_in_use
+        return (counts, arch.first(counts.released)) if archive else counts
+
+    def restore_enqueue(self, archive: BrickArchive, record: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """mipsf_sparse_restore of the archive's entries (its first ``n`` when that is known); nothing is read back.  The bricks get
+        slots behind the ones in use, in ascending brick index, and their words; a brick that has a slot keeps what it holds
+        -> record int64 [7] on the device (RestoreCounts' fields)"""
+        if not isinstance(archive, BrickArchive):
+            raise ValueError(f"restore: expected a BrickArchive, got {type(archive).__name__}")
+        if (archive.born is None) != (not self.history):
+            raise ValueError("restore: an archive with born goes with a volume made with history=True, one without with history=False")
+        if (archive.color is None) != (self.color is None):
+            raise ValueError("restore: an archive with color goes with a volume made with color=True, one without with color=False")
+        arch = archive if archive.n is None else archive.first(archive.n)
+        m = len(arch)
+        if m > _lib.SPARSE_MAX_CAPACITY:
+            raise ValueError(f"restore: {m} entries, at most {_lib.SPARSE_MAX_CAPACITY} a call")
+        with torch.cuda.device(self.device):
+            if m and arch.bricks.device != self.device:
+                arch = arch.to(self.device)
+            record = torch.empty(_lib.SPARSE_RESTORE_RECORD_WORDS, dtype=torch.int64, device=self.device) if record is None else record
+            scratch = torch.empty(_lib.SPARSE_RESTORE_SCRATCH_WORDS // 2, dtype=torch.int64, device=self.device)
+            a = _lib.SparseRestoreArgs.new(m=m, vol=self._vol, born=_lib.dptr(self.born, torch.int32),
+                                           arch_brick=_lib.dptr(arch.bricks.contiguous(), torch.int32) if m else None,
+                                           arch_born=_lib.dptr(arch.born.contiguous(), torch.int32) if m and arch.born is not None else None,
+                                           arch_tsdf=_lib.dptr(arch.tsdf.contiguous()) if m else None,
+                                           arch_weight=_lib.dptr(arch.weight.contiguous()) if m else None,
+                                           arch_color=_lib.dptr(arch.color.contiguous()) if m and arch.color is not None else None,
+                                           mark=self._mark.data_ptr(), scan=self._scan.data_ptr(), scratch=_lib.dptr(scratch, torch.int64),
+                                           record=_lib.dptr(record, torch.int64))
+            _lib.check(_lib.lib().mipsf_sparse_restore(C.byref(a), _lib.stream_ptr()), "sparse_restore")
+        if m:
+            self.bricks_in_use = None
+        return record
+
+    def restore(self, archive: BrickArchive) -> RestoreCounts:
+        """Brings the bricks of a BrickArchive back: each gets a slot and the words it left with (and its ``born``); of two entries of
+        one brick the first wins; a brick that has a slot meanwhile keeps what it holds (``occupied``); bricks that find the pool
+        full are ``dropped``.  One read-back."""
+        with torch.cuda.device(self.device):
+            counts = RestoreCounts(*(int(x) for x in self.restore_enqueue(archive).tolist()))
+        if counts.listed:
+            self.bricks_in_use = counts.bricks_in_use
+        return counts
 
     def allocated_bricks(self) -> np.ndarray:
         """the bricks in use, in slot order -> int64 [m,3] brick coordinates (one read-back of slot_brick)"""
         got = torch.cat([self.count, self.slot_brick]).cpu().numpy().astype(np.int64)
-        b = got[1:1 + min(int(got[0]), self.capacity)]
+        self.bricks_in_use = min(int(got[0]), self.capacity)
+        b = got[1:1 + self.bricks_in_use]
         return np.stack([b // (self.bricks[1] * self.bricks[2]), (b // self.bricks[2]) % self.bricks[1], b % self.bricks[2]], 1)
 
     def tight_window(self):
@@ -560,12 +752,16 @@ def sparse_tsdf_mesh_from_frames(depth, c2w, K, voxel_size: float, capacity_bric
 
 def sparse_tsdf_odometry(depth, K, first_pose, voxel_size: float, bounds, capacity_bricks: int, trunc: Optional[float] = None, rgb=None,
                          min_correspondences: int = 0, device=None, color_weight: Optional[float] = None, band: Optional[float] = None,
-                         **track_kw):
+                         keep_radius: Optional[float] = None, **track_kw):
     """tsdf_odometry over a SparseTSDFVolume: frame 0 is fused at ``first_pose``; every later frame is registered against the ray
     cast from the previous frame's pose and fused (bricks allocated first) at the pose found.  The walk is enqueued whole; one
     read-back at the end.  A lost frame is fused at a NaN pose, which allocates and updates nothing.
     -> (poses fp32 [n,4,4] on the host, records, SparseTSDFVolume); the records are tsdf_odometry's, and the last one also holds
-    ``dropped`` (bricks that found no slot, over all frames) and ``bricks_in_use``."""
+    ``dropped`` (bricks that found no slot, over all frames) and ``bricks_in_use``.  With ``keep_radius`` (metres) the bricks that
+    lie wholly outside the box [t - keep_radius, t + keep_radius] around the position t of the pose a frame was fused at are released
+    after that frame's fusion, so a pool smaller than the scene follows the camera; the box is made on the device (no read-back), a
+    lost frame has a NaN pose and releases nothing, every record then also holds that frame's ``dropped`` and ``released``, and the
+    last one the sum ``released_total`` (its ``dropped`` stays the sum over all frames).  Without it the launches are those of before."""
     if color_weight is not None and rgb is None:
         raise ValueError("color_weight: tracking with colour needs rgb")
     voxel_size = float(voxel_size)
@@ -586,7 +782,16 @@ def sparse_tsdf_odometry(depth, K, first_pose, voxel_size: float, bounds, capaci
         lost = torch.zeros(n, dtype=torch.bool, device=dev)
         poses[0] = _poses(first_pose, dev)[0]
         nan_pose = torch.full((4, 4), math.nan, dtype=torch.float32, device=dev)
+        if keep_radius is not None and not (float(keep_radius) >= 0 and math.isfinite(float(keep_radius))):
+            raise ValueError(f"keep_radius {keep_radius} is negative, infinite or not a number")
+        reach = None if keep_radius is None else torch.tensor([-float(keep_radius)] * 3 + [float(keep_radius)] * 3, dtype=torch.float64, device=dev)
+        released = []
+
+        def let_go(pose):                                # the box around where the frame was fused, from the device's words
+            if reach is not None:
+                released.append(vol.release_enqueue(pose[:3, 3].to(torch.float64).repeat(2) + reach))
         allocs = [vol.integrate_enqueue(D[:1], poses[:1], K, None if C3 is None else C3[:1])[1]]
+        let_go(poses[0])
         for k in range(1, n):
             prev = poses[k - 1]
             if color_weight is None:
@@ -596,13 +801,23 @@ def sparse_tsdf_odometry(depth, K, first_pose, voxel_size: float, bounds, capaci
             bad = result[16] < float(min_correspondences)
             poses[k] = torch.where(bad, prev, pose)
             results[k], lost[k] = result, bad
-            allocs.append(vol.integrate_enqueue(D[k:k + 1], torch.where(bad, nan_pose, pose)[None], K, None if C3 is None else C3[k:k + 1])[1])
-        got = torch.cat([poses.reshape(n, 16).to(torch.float64), results, lost[:, None].to(torch.float64),
-                         torch.stack(allocs).to(torch.float64)], 1).cpu()
+            fused_at = torch.where(bad, nan_pose, pose)
+            allocs.append(vol.integrate_enqueue(D[k:k + 1], fused_at[None], K, None if C3 is None else C3[k:k + 1])[1])
+            let_go(fused_at)
+        got = torch.cat([poses.reshape(n, 16).to(torch.float64), results] + ([torch.stack(released).to(torch.float64)] if released else [])
+                        + [lost[:, None].to(torch.float64), torch.stack(allocs).to(torch.float64)], 1).cpu()
     records = [{"transformation": r[16:32].reshape(4, 4).clone(), "n_correspondences": int(r[32]), "fitness": float(r[33]),
                 "inlier_rmse": float(r[34]), "iterations": int(r[35]), "lost": bool(r[-5])} for r in got]
     if color_weight is not None:
         for rec, r in zip(records, got):
             rec["n_color"], rec["color_rmse"] = int(r[36]), float(r[37])
     records[-1]["dropped"], records[-1]["bricks_in_use"] = int(got[:, -2].sum()), int(got[-1, -1])
+    if released:
+        at = 16 + words
+        for rec, r in zip(records, got):
+            rec["dropped"], rec["released"] = int(r[-2]), int(r[at + 1])
+        records[-1]["dropped"], records[-1]["released_total"], records[-1]["bricks_in_use"] = int(got[:, -2].sum()), int(got[:, at + 1].sum()), int(got[-1, at + 6])
+        vol.bricks_in_use = int(got[-1, at + 6])
+    else:
+        vol.bricks_in_use = int(got[-1, -1])
     return got[:, :16].reshape(n, 4, 4).to(torch.float32), records, vol
