@@ -76,6 +76,31 @@ def large_ms(cu_count):
     return (P - 32, P, P + 33)
 
 
+def tile_edge_ms(cu_count):
+    """Both weight-gradient kernels launch min(tiles, T) workgroups, T = min(CU count, 256) (WG_MAX_BLOCKS / W16_MAX_BLOCKS).  The
+    streaming kernel (wgrad16.hip) counts 32-sample tiles: 32 T - 31 gives T tiles, the last one ragged; 32 T + 1 gives T + 1,
+    so one workgroup takes two.  The LDS kernel (decoder.hip) counts 128-sample block tiles: 128 T + 1 is the same edge for it
+    (T + 1 block tiles, the last one a single sample)."""
+    T = min(cu_count, 256)
+    return (32 * T - 31, 32 * T + 1, 128 * T + 1)
+
+
+def form_cases(cu_count):
+    """[(M, variant)]: where the further weight-gradient forms of tests/test_gpu_decoder_fp64.py (BWD_FORMS2) run -- the smallest
+    sizes at which they can go wrong: one tile and a sample, four tiles and a sample (also with subnormal rows), more tiles than
+    the small-batch chain has waves, the workgroup-count edges, and the persistent chain with a ragged tile"""
+    return ([(33, "base"), (129, "base"), (129, "subnormal"), (4096 + 17, "base")]
+            + [(M, "base") for M in tile_edge_ms(cu_count)] + [(large_ms(cu_count)[2], "base")])
+
+
+def live_tiles(dout):
+    """the 32-sample tiles with a non-zero incoming gradient, ascending: what the backward chain appends to its live-tile lists
+    (decoder16.hip tl_append: tile t goes to list (t >> 3) & 7)"""
+    M = dout.shape[0]
+    live = torch.cat([(dout != 0).any(1), torch.zeros((-M) % 32, dtype=torch.bool)])
+    return live.view(-1, 32).any(1).nonzero()[:, 0]
+
+
 # ------------------------------------------------------------------------------------------------------- encoding
 def freq_scale(dtype):
     """[8] 2^k pi_f (exact in fp32)"""
@@ -121,9 +146,10 @@ def forward(weights, feat, x, pe):
 
 
 # ------------------------------------------------------------------------------------------------------- backward
-def backward(weights, feat, fwd, dpe_dx, dout, term_norms=False):
+def backward(weights, feat, fwd, dpe_dx, dout, term_norms=False, cut=None):
     """by hand from dout [M,10] -> dfeat [M,32], dx_direct [M,3] (through e's first three columns), dembed_pos [M,48], dx (direct
-    plus the path through the encoding) and the ten parameter gradients in ops.DECODER_PARAM_ORDER"""
+    plus the path through the encoding) and the ten parameter gradients in ops.DECODER_PARAM_ORDER.  cut = (kind, pieces): the
+    gradients CUTS[kind] names are formed from operands cut to ``pieces`` bf16 pieces (``cut_product``), still in float64"""
     w0, b0, w2, b2, wr, br, ws0, bs0, ws2, bs2 = weights
     e, H1, H2, G3, p = fwd["e"], fwd["H1"], fwd["H2"], fwd["G3"], fwd["prob"]
     M = e.shape[0]
@@ -149,15 +175,107 @@ def backward(weights, feat, fwd, dpe_dx, dout, term_norms=False):
     dx = dx_direct + (dpe.reshape(M, 3, N_FREQ, 2) * dpe_dx).sum((-1, -2))
     res = dict(dfeat=dfeat, dx_direct=dx_direct, dembed_pos=dpe, dx=dx,
                grads=[g_w0, g_b0, g_w2, g_b2, g_wr, g_br, g_ws0, g_bs0, g_ws2, g_bs2])
+    # every parameter gradient is d^T a (a = None: a bias, the column sums of d), in ops.DECODER_PARAM_ORDER
+    pairs = [(dH1, e), (dH1, None), (dH2, torch.relu(H1)), (dH2, None), (drgb, torch.cat([H2[:, N_SDF_EMB:], e], 1)), (drgb, None),
+             (dG3, torch.cat([H2[:, :N_SDF_EMB], feat], 1)), (dG3, None), (dlogits, A3), (dlogits, None)]
+    if cut is not None:
+        kind, pieces = cut
+        for i, n_cut in CUTS[kind].items():
+            res["grads"][i] = cut_product(*pairs[i], pieces) if n_cut else res["grads"][i]
     if term_norms:
-        # sqrt(sum_i t_i^2) of every entry's sum over the samples, t_i = d[i, j] a[i, k] (a = 1 for a bias): ``summation_floor``
+        # sqrt(sum_i t_i^2) of every entry's sum over the samples, t_i = d[i, j] a[i, k] (a = 1 for a bias): ``summation_floor``;
+        # sum_i |t_i|, the magnitude a relative error of every term is applied to: ``two_plane_bound``
         sq = lambda d, a=None: ((d * d).T @ (a * a) if a is not None else (d * d).sum(0)).sqrt()      # noqa: E731
-        res["term_norms"] = [sq(dH1, e), sq(dH1), sq(dH2, torch.relu(H1)), sq(dH2), sq(drgb, torch.cat([H2[:, N_SDF_EMB:], e], 1)),
-                             sq(drgb), sq(dG3, torch.cat([H2[:, :N_SDF_EMB], feat], 1)), sq(dG3), sq(dlogits, A3), sq(dlogits)]
+        ab = lambda d, a=None: (d.abs().T @ a.abs() if a is not None else d.abs().sum(0))              # noqa: E731
+        res["term_norms"] = [sq(d, a) for d, a in pairs]
+        res["term_abs"] = [ab(d, a) for d, a in pairs]
     return res
 
 
-def evaluate(weights32, feat32, x32, dout32, dtype, *, external=False, shift_sin=0.0, shift_cos=0.0, term_norms=False):
+# ------------------------------------------------------------------------------------- the two-plane bf16 arithmetics
+# Which parameter gradients (index in ops.DECODER_PARAM_ORDER) a two-plane arithmetic forms from cut operands, and how many of
+# a term's factors are cut (2: both, the gradient and the activation; 1: the gradient alone -- a bias), read in the kernels:
+#
+#   "lds"     wgrad_precision="bf16x3", decoder.hip decoder_wgrad_kernel<.., BF16X3 = true>: wgrad_mma_bf16 runs the three LARGE
+#             products -- sdf0: dG3^T [sdf_emb | grid], pts2: dH2^T relu(H1), pts0: dG1^T [e | ones] -- and split8_bf16 cuts BOTH
+#             operands as they come out of LDS: hi = (__bf16)v, lo = (__bf16)(v - (float)hi), both conversions round to nearest
+#             even; per k-step hi hi + hi lo + lo hi, the lo lo pair is dropped; fp32 accumulators.  The ones row of the pts0
+#             phase makes column 51 of that product d pts_linears.0.bias: it IS a cut product, with 1.0 (exact in bf16, lo = 0)
+#             as its second factor.  The two small heads (wgrad_mma_small, fp32-input MFMA) and the other four biases (row_sum in
+#             fp32, the ones column of the small product) are not cut.
+#   "stream"  wgrad_precision="stream_bf16x3", wgrad16.hip ArBF2 (P = 2), the streaming form w16_role_a / w16_role_b: next_plane
+#             cuts EVERY block it transposes -- the five gradient blocks (dH2, dG3, dG1 and the small rows d logits | d rgb) in
+#             transpose_block, the five activation blocks (H1, H3, sdf_emb | grid, rgb_emb, e) in transpose_mac -- into plane 0 =
+#             bf16(r) (v_cvt_pk_bf16_f32, round to nearest even), r -= plane 0 (exact in fp32), plane 1 = bf16(r); the products
+#             keep the plane pairs pa + pb <= 1, again hi hi + hi lo + lo hi.  All five bias gradients are the row sums of the
+#             TRANSPOSED PLANES of their gradient block (transpose_block<A, SUM = true>): hi + lo, one cut factor.  So here the
+#             small heads and every bias go through the cut as well.
+CUTS = {"lds": {0: 2, 1: 1, 2: 2, 6: 2},
+        "stream": {0: 2, 1: 1, 2: 2, 3: 1, 4: 2, 5: 1, 6: 2, 7: 1, 8: 2, 9: 1}}
+U_BF16 = 2.0 ** -8                     # bf16 keeps 8 significant bits: round to nearest is within 2^-8 of the value
+# two pieces: |v - hi| <= 2^-8 |v|, lo = bf16(v - hi) is within 2^-8 of THAT: v = (hi + lo)(1 + d), |d| <= 2^-16
+CUT_ONE = U_BF16 ** 2
+# both factors cut and the lo lo pair dropped: (a_hi + a_lo)(b_hi + b_lo) - a_lo b_lo; the first is a b (1 + d_a)(1 + d_b), and
+# |a_lo| <= 2^-8 (1 + 2^-8) |a|: a term is within (2 * 2^-16 + 2^-32 + 2^-16 (1 + 2^-8)^2) |a b|, 3.008 * 2^-16
+CUT_BOTH = 2 * CUT_ONE + CUT_ONE ** 2 + (U_BF16 * (1 + U_BF16)) ** 2
+
+
+def bf16_pieces(v, pieces):
+    """-> (hi, lo) float64: the fp32 value of ``v`` (what the records hold) as the kernels cut it: hi = bf16(v), lo = bf16(v - hi)
+    (the difference is exact in fp32), both round to nearest even; pieces = 1: lo = 0"""
+    v32 = v.float()
+    hi = v32.to(torch.bfloat16).float()
+    lo = (v32 - hi).to(torch.bfloat16).float() if pieces == 2 else torch.zeros_like(hi)
+    return hi.double(), lo.double()
+
+
+def cut_product(d, a, pieces):
+    """d^T a (a None: the column sums of d) in float64 from operands cut to ``pieces`` bf16 pieces, the lo lo pair dropped"""
+    dh, dl = bf16_pieces(d, pieces)
+    if a is None:
+        return (dh + dl).sum(0)
+    ah, al = bf16_pieces(a, pieces)
+    return dh.T @ ah + dh.T @ al + dl.T @ ah
+
+
+def two_plane_bound(ref, kind):
+    """{parameter name: (bound [like the gradient], bound on the rms)} for the gradients ``kind`` ("lds" / "stream", CUTS) forms
+    from cut operands, on the error over the tensor's largest float64 magnitude (``errors``' normalisation); the other
+    gradients keep ``gates``.
+
+    Per element: a cut term is within c |t_i| of the float64 term (c = CUT_BOTH for a weight, CUT_ONE for a bias, derived
+    above from the two roundings to nearest of the cut), so the sum of the cut terms is within c A of the float64 sum, A = sum_i
+    |t_i| in float64 (``backward(term_norms=True)``: term_abs) -- a worst-case bound, as tests/hashgrid_cpu.py's gamma(k) A.
+    What the kernel does besides -- the fp32 record it cuts, the fp32 accumulators, the reduce -- is the fp32 arithmetic the
+    existing gate (a) allows for, and is added: bound = c A / max |r64| + gate (a).  The rms over the tensor: the two parts'
+    rms add (the triangle inequality): rms(c A / max |r64|) + gate (b)."""
+    out = {}
+    for i, n_cut in CUTS[kind].items():
+        name, g = ops.DECODER_PARAM_ORDER[i], ref["r64"]["grads"][i]
+        top = float(g.abs().max())
+        part = (CUT_BOTH if n_cut == 2 else CUT_ONE) * ref["term_abs"][i] / (top if top > 0 else 1.0)
+        g_max, g_rms = gates(name, ref["e32"][name], ref["extra"][name])
+        out[name] = (part + g_max, float(part.pow(2).mean().sqrt()) + g_rms)
+    return out
+
+
+def two_plane_errors(grads, ref, kind):
+    """{name: dict(share: the largest error / bound over the elements, where, max: the error there, bound: the bound there,
+    rms, rms_bound)} of the ten ``grads`` for the gradients ``kind`` cuts"""
+    out = {}
+    for name, (bound, rms_bound) in two_plane_bound(ref, kind).items():
+        i = ops.DECODER_PARAM_ORDER.index(name)
+        r = ref["r64"]["grads"][i]
+        top = float(r.abs().max())
+        err = (grads[i].double() - r).abs() / (top if top > 0 else 1.0)
+        share = (err / bound).reshape(-1)
+        w = int(torch.argmax(share))
+        out[name] = dict(share=float(share[w]), where=w, max=float(err.reshape(-1)[w]), bound=float(bound.reshape(-1)[w]),
+                         rms=float(err.pow(2).mean().sqrt()), rms_bound=rms_bound)
+    return out
+
+
+def evaluate(weights32, feat32, x32, dout32, dtype, *, external=False, shift_sin=0.0, shift_cos=0.0, term_norms=False, cut=None):
     """forward and backward in ``dtype`` from the fp32 inputs.  external: the encoding is an INPUT, the fp32 tensor
     ``embed_pos(x32)`` (MLP_reg's embed_pos argument), and dx is the direct path alone -- what the kernels return then."""
     if external:
@@ -169,7 +287,7 @@ def evaluate(weights32, feat32, x32, dout32, dtype, *, external=False, shift_sin
     fwd = forward(w, feat32.to(dtype), x32.to(dtype), pe)
     res = dict(out=fwd["out"], H1=fwd["H1"], H2=fwd["H2"], G3=fwd["G3"])
     if dout32 is not None:
-        res.update(backward(w, feat32.to(dtype), fwd, dpe_dx, dout32.to(dtype), term_norms))
+        res.update(backward(w, feat32.to(dtype), fwd, dpe_dx, dout32.to(dtype), term_norms, cut))
     return res
 
 
@@ -356,7 +474,8 @@ def _reference(M, seed, variant, external):
     # in front of it.  The yardstick carries it too and 8 e32 covers it -- except where the yardstick is EXACT: the bias
     # gradients of a batch of one sample are that sample's dout, an input (e32 = 0, and gate (b) would be 0).  From float64
     # alone: the errors of r64 * (1 + 2^-24) under the same normalisations; the larger of it and the encoding's allowance.
-    rounding = errors({k: ([g * (1.0 + U) for g in v] if k == "grads" else v * (1.0 + U)) for k, v in r64.items() if k != "term_norms"},
+    rounding = errors({k: ([g * (1.0 + U) for g in v] if k == "grads" else v * (1.0 + U)) for k, v in r64.items()
+                       if k not in ("term_norms", "term_abs")},
                       r64, c["dout"])
     extra = {k: dict(max=max(v["max"], rounding[k]["max"]), rms=max(v["rms"], rounding[k]["rms"]), where=v["where"])
              for k, v in extra.items()}
@@ -364,14 +483,17 @@ def _reference(M, seed, variant, external):
         extra[k] = dict(max=max(extra[k]["max"], v["max"]), rms=max(extra[k]["rms"], v["rms"]), where=extra[k]["where"])
     # (the pre-activations of a large case are 400 MB: what a report needs of them is each sample's distance from a threshold)
     margin = torch.minimum(r64["H1"].abs().min(1).values, r64["G3"].abs().min(1).values)
-    r64 = {k: v for k, v in r64.items() if k not in ("H1", "H2", "G3", "term_norms")}
-    return dict(case=c, r64=r64, e32=e32, e32_normal=e32_normal, extra=extra, flips=flips, margin=margin)
+    term_abs = r64["term_abs"]
+    r64 = {k: v for k, v in r64.items() if k not in ("H1", "H2", "G3", "term_norms", "term_abs")}
+    return dict(case=c, r64=r64, e32=e32, e32_normal=e32_normal, extra=extra, flips=flips, margin=margin, term_abs=term_abs)
 
 
 # The seed of a size's cases, chosen by hand where seed 1 left the fp32 yardstick less than its headroom on the host this was
 # written on (a cancelling bias gradient of a few samples).  A fixed table, so every machine builds the same inputs;
 # tests/test_decoder_cpu.py asserts the headroom for every case, and that assertion is the host's fp32 figure.
-SEEDS = {31: 2, 32: 2, 33: 2}
+# 32769 (128 * 256 + 1, tile_edge_ms): seed 1 puts the summation floor of pts_linear.2.weight at 4.25e-6, above GATE_FLOOR, and gate
+# (a) is to stay at GATE_FLOOR in every case (a float64 figure; tests/test_decoder_cpu.py asserts it).
+SEEDS = {31: 2, 32: 2, 33: 2, 32769: 2}
 
 
 @functools.lru_cache(maxsize=None)
@@ -395,5 +517,6 @@ def reference(M, variant="base", external=False):
     """-> dict: ``case``, ``r64`` (the answer), ``e32`` (the yardstick's errors; ``e32_normal``: without the subnormal rows),
     ``extra`` (the allowance for the hardware sine and cosine: EXTRA_FACTOR times the change of the answer under the shifted
     encoding, and at least the result's own rounding -- that alone for the external form, whose encoding is an input), ``flips`` (live samples whose ReLU pattern changes under
-    the shift), ``margin`` [M] (each sample's smallest float64 |pre-activation| of H1 and G3)"""
+    the shift), ``margin`` [M] (each sample's smallest float64 |pre-activation| of H1 and G3), ``term_abs`` (per parameter gradient
+    the float64 sum over the samples of its terms' magnitudes: ``two_plane_bound``)"""
     return _reference(M, pick_seed(M, variant), variant, external)

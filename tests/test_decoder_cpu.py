@@ -6,7 +6,11 @@ tests/test_gpu_decoder_fp64.py compares the kernels with an answer that is itsel
   * the derivative of the encoding equals a central difference of the float64 sine at the fp32 argument;
   * every case the GPU module uses meets the conditions on its inputs: the threshold share, the planted samples live, zero tiles
     and partially zero tiles present, the yardstick's headroom under GATE_FLOOR (a figure of the host's fp32 sums), the allowance
-    for the hardware sine under GATE_FLOOR for the outputs, the summation floor of the parameter gradients under GATE_FLOOR.  The large cases depend on the device's CU count: checked with 256 and with 64."""
+    for the hardware sine under GATE_FLOOR for the outputs, the summation floor of the parameter gradients under GATE_FLOOR.  The large cases depend on the device's CU count: checked with 256 and with 64;
+  * the cases of the list forms hold zero tiles and mixed tiles, and those of the ordered lists give every list something to put
+    in order;
+  * the bound of the two-plane bf16 arithmetics (decoder_cpu.two_plane_bound) holds for the float64 backward with exactly those
+    operands cut to two bf16 pieces, and is exceeded when they are cut to one."""
 import math
 
 import pytest
@@ -20,6 +24,8 @@ from . import step_cpu
 
 SMALL = [(M, v) for v in D.VARIANTS for M in D.SMALL_MS]
 LARGE = [(M, "base") for cu in (256, 64) for M in D.large_ms(cu)]
+EDGE = sorted({(M, "base") for cu in (256, 64) for M in D.tile_edge_ms(cu)})
+FORM_CASES = sorted({mv for cu in (256, 64) for mv in D.form_cases(cu)})
 
 
 def rel(a, b):
@@ -69,7 +75,7 @@ def test_encoding_derivative_against_a_central_difference():
     assert pe32.dtype == torch.float32 and float((pe32.double() - torch.sin(arg).reshape(129, -1)).abs().max()) <= 2.0 ** -24
 
 
-@pytest.mark.parametrize("M,variant", SMALL + LARGE, ids=lambda v: str(v))
+@pytest.mark.parametrize("M,variant", SMALL + LARGE + EDGE, ids=lambda v: str(v))
 def test_every_case_meets_the_conditions_on_its_inputs(M, variant):
     ref = D.reference(M, variant)
     c = ref["case"]
@@ -133,3 +139,69 @@ def test_gates_and_errors():
         err = D.errors(dict(grads=bad["grads"]), r64, c["dout"])
         worst = max(err[n]["max"] / D.gates(n, ref["e32"][n], ref["extra"][n])[0] for n in ops.DECODER_PARAM_ORDER)
         assert worst > 10.0, (what, worst)
+
+
+@pytest.mark.parametrize("cu", (256, 64))
+def test_cases_of_the_list_forms_have_zero_tiles_mixed_tiles_and_lists_to_order(cu):
+    """The live-tile-list forms (COMPACT_LIVE off) are exercised only where the chain skips a tile and keeps a tile with dead rows
+    in it; the ordered lists (deterministic=True) only where a list has several members, handed in by several workgroups."""
+    T = min(cu, 256)
+    for M, variant in D.form_cases(cu):
+        if M >= 129:
+            zero, mixed = D.zero_tiles(D.case(M, variant)["dout"])
+            assert zero >= 1 and mixed >= 1, (M, variant, zero, mixed)
+    t_minus, t_plus, _ = D.tile_edge_ms(cu)
+    assert ((t_minus + 31) // 32, (t_plus + 31) // 32) == (T, T + 1) and t_minus % 32 == 1, "T tiles, the last ragged; T + 1 tiles"
+    assert (D.tile_edge_ms(cu)[2] + 127) // 128 == T + 1
+    # P + 33: more live tiles than the weight-gradient kernel has workgroups, so every workgroup walks several list positions
+    big = D.live_tiles(D.case(D.large_ms(cu)[2])["dout"])
+    assert big.numel() > T, (big.numel(), T)
+    # 32 T + 1 has T + 1 tiles, one of them zero at the least (above): it cannot hold more than T live ones.  What the ordering
+    # needs there: every one of the eight lists has several members (a list of one is in order whatever the schedule)
+    for M in (t_plus, D.large_ms(cu)[2]):
+        tiles = D.live_tiles(D.case(M)["dout"])
+        for q in range(8):
+            mine = tiles[((tiles >> 3) & 7) == q]
+            assert mine.numel() >= 2, (M, q, mine.tolist())
+
+
+@pytest.mark.parametrize("M,variant", FORM_CASES, ids=lambda v: str(v))
+def test_two_plane_bound_holds_for_two_pieces_and_not_for_one(M, variant):
+    """(a) the float64 backward with exactly the operands a two-plane arithmetic cuts (decoder_cpu.CUTS) rounded to two bf16
+    pieces, the lo lo pair dropped, stays inside decoder_cpu.two_plane_bound, element by element and in the rms; (b) with one piece
+    it does not, at any size.  Measured on the host this was written on: (a) 0.34 of the bound at M = 33, 0.25 at 129, 0.08 at
+    4113, 0.02 - 0.12 at the larger sizes; (b) 110 x the bound at M = 33, 120 x at 129, 33 x at 4113, 12 x at 131105."""
+    ref = D.reference(M, variant)
+    c = ref["case"]
+    want = ref["r64"]["grads"]
+    # (the streaming form cuts all ten gradients, the lds form four of them in the same way: one evaluation per number of pieces)
+    cut = {pieces: D.evaluate(c["weights"], c["feat"], c["x"], c["dout"], torch.float64, cut=("stream", pieces))["grads"] for pieces in (2, 1)}
+    for kind in D.CUTS:
+        shares = []
+        for pieces in (2, 1):
+            e = D.two_plane_errors([g if i in D.CUTS[kind] else r for i, (g, r) in enumerate(zip(cut[pieces], want))], ref, kind)
+            assert set(e) == {ops.DECODER_PARAM_ORDER[i] for i in D.CUTS[kind]}
+            shares.append(max(max(v["share"], v["rms"] / v["rms_bound"]) for v in e.values()))
+            if pieces == 2:
+                for name, v in e.items():
+                    assert v["share"] <= 1.0 and v["rms"] <= v["rms_bound"], \
+                        f"{kind} {name}: element {v['where']} {v['max']:.3e} over its bound {v['bound']:.3e}; rms {v['rms']:.3e} ({v['rms_bound']:.3e})"
+        print(f"\n  two-plane bound | {kind} | M{M}-{variant} | two pieces {shares[0]:.3f} | one piece {shares[1]:.1f}", end="")
+        assert shares[1] > 1.0, f"{kind}: one bf16 piece stays inside the two-plane bound ({shares[1]:.2f}): the bound has no teeth"
+
+
+def test_two_plane_constants_and_cut():
+    v = torch.tensor([1.0 + 2.0 ** -7 + 2.0 ** -15 + 2.0 ** -23, -3.1415926, 1e-30, 0.0], dtype=torch.float64)
+    hi, lo = D.bf16_pieces(v, 2)
+    assert bool(((v.float().double() - hi - lo).abs() <= D.CUT_ONE * v.abs()).all()) and bool((lo.abs() <= D.U_BF16 * (1 + D.U_BF16) * v.abs()).all())
+    assert float(hi[0]) == 1.0 + 2.0 ** -7 and float(lo[0]) == 2.0 ** -15, "round to nearest even of the exact residual 2^-15 + 2^-23"
+    assert D.bf16_pieces(v, 1)[1].count_nonzero() == 0
+    assert 3.0 * 2.0 ** -16 < D.CUT_BOTH < 3.01 * 2.0 ** -16 and D.CUT_ONE == 2.0 ** -16
+    # the lds form leaves the small heads and four biases alone; the streaming form cuts all ten
+    assert sorted(D.CUTS["lds"]) == [0, 1, 2, 6] and sorted(D.CUTS["stream"]) == list(range(10))
+    assert all(n == (1 if ops.DECODER_PARAM_ORDER[i].endswith("bias") else 2) for k in D.CUTS for i, n in D.CUTS[k].items())
+    c, want = D.case(33), D.reference(33)["r64"]["grads"]
+    lds, stream = (D.evaluate(c["weights"], c["feat"], c["x"], c["dout"], torch.float64, cut=(k, 2))["grads"] for k in ("lds", "stream"))
+    for i in range(10):
+        assert torch.equal(lds[i], stream[i] if i in D.CUTS["lds"] else want[i]), "only the listed gradients are cut, alike in both forms"
+        assert not torch.equal(stream[i], want[i])
