@@ -5,6 +5,7 @@ operator raises when its tensors are not on a GPU.
 """
 from __future__ import annotations
 
+import contextlib
 import ctypes as C
 import os
 from typing import Optional
@@ -578,6 +579,35 @@ def hashgrid_counter_layout(meta) -> dict:
             "n_bins": bins}
 
 
+def _all_signatures():
+    return (list(SIGNATURES.items()) + list(MESH_SIGNATURES.items())
+            + list(FUSE_SIGNATURES.items()) + list(ICP_SIGNATURES.items())
+            + list(COMPACT_SIGNATURES.items()) + list(POSEGRAPH_SIGNATURES.items())
+            + list(SUBMAP_SIGNATURES.items()) + list(EVAL_SIGNATURES.items())
+            + list(RASTER_SIGNATURES.items()) + list(TSDF_SIGNATURES.items())
+            + list(IMAGE_SIGNATURES.items()) + list(TRACK_SIGNATURES.items()) + list(TRACK_COLOR_SIGNATURES.items())
+            + list(SHADE_SIGNATURES.items()) + list(SPARSE_SIGNATURES.items())
+            + list(SPARSE_MESH_SIGNATURES.items()) + list(DEINTEGRATE_SIGNATURES.items())
+            + list(SPARSE_REMOVE_SIGNATURES.items()) + list(SPARSE_RELEASE_SIGNATURES.items()))
+
+
+def load(path: str) -> C.CDLL:
+    """A build of the C ABI as a fresh handle with every signature applied and the ABI version checked; it is returned, not
+    kept: lib() keeps the product's, use_library() lends a variant's (csrc/variants.mk) to a block of calls."""
+    if not os.path.exists(path):
+        raise RuntimeError(
+            f"{path} is missing: build it with `python -c 'import __graft_entry__ as g; g.build()'` "
+            "(or `make -C mipsfusion_amd/csrc all variants`). There is no CPU fallback.")
+    handle = C.CDLL(path)
+    for name, (res, args) in _all_signatures():
+        fn = getattr(handle, name)
+        fn.restype = res
+        fn.argtypes = args
+    if handle.mipsf_abi_version() != 2:
+        raise RuntimeError(f"{os.path.basename(path)} ABI version mismatch")
+    return handle
+
+
 _lib: Optional[C.CDLL] = None
 
 
@@ -585,27 +615,39 @@ def lib() -> C.CDLL:
     """Load (once) and return the shared library; raises if it has not been built."""
     global _lib
     if _lib is None:
-        if not os.path.exists(LIB_PATH):
-            raise RuntimeError(
-                f"{LIB_PATH} is missing: build it with `python -c 'import __graft_entry__ as g; g.build()'` "
-                "(or `make -C mipsfusion_amd/csrc`). There is no CPU fallback.")
-        handle = C.CDLL(LIB_PATH)
-        for name, (res, args) in list(SIGNATURES.items()) + (list(MESH_SIGNATURES.items())
-                                       + list(FUSE_SIGNATURES.items()) + list(ICP_SIGNATURES.items())
-                                       + list(COMPACT_SIGNATURES.items()) + list(POSEGRAPH_SIGNATURES.items())
-                                       + list(SUBMAP_SIGNATURES.items()) + list(EVAL_SIGNATURES.items())
-                                       + list(RASTER_SIGNATURES.items()) + list(TSDF_SIGNATURES.items())
-                                       + list(IMAGE_SIGNATURES.items()) + list(TRACK_SIGNATURES.items()) + list(TRACK_COLOR_SIGNATURES.items())
-                                       + list(SHADE_SIGNATURES.items()) + list(SPARSE_SIGNATURES.items())
-                                       + list(SPARSE_MESH_SIGNATURES.items()) + list(DEINTEGRATE_SIGNATURES.items())
-                                       + list(SPARSE_REMOVE_SIGNATURES.items()) + list(SPARSE_RELEASE_SIGNATURES.items())):
-            fn = getattr(handle, name)
-            fn.restype = res
-            fn.argtypes = args
-        if handle.mipsf_abi_version() != 2:
-            raise RuntimeError("libmipsf_hip.so ABI version mismatch")
-        _lib = handle
+        _lib = load(LIB_PATH)
     return _lib
+
+
+def variant_path(name: str) -> str:
+    """The variant library `name` of csrc/variants.mk, where `make variants` leaves it."""
+    return os.path.join(_HERE, "variants", f"libmipsf_{name}.so")
+
+
+@contextlib.contextmanager
+def use_library(path: str):
+    """Every call inside the block goes to the build at `path` (a variant library, or any build of the same C ABI): lib()
+    returns its handle, so ops.* and every size query (mipsf_buffer_size: the variant's own plan) run unchanged.  The kept
+    counter / ticket blocks are dropped on entry and on exit -- a block sized and left behind by one build's plan must not be
+    handed to another build's kernels.  The device is synchronised first: a dropped block may still be in use by a launch in
+    flight.  Not for concurrent use: the handle is a module global."""
+    global _lib
+    handle = load(path)
+
+    def drop_kept_blocks():
+        if torch.cuda.is_available() and torch.cuda.is_initialized():
+            torch.cuda.synchronize()
+        for cache in KEPT_BLOCK_CACHES:
+            cache.clear()
+
+    previous = _lib
+    drop_kept_blocks()
+    _lib = handle
+    try:
+        yield handle
+    finally:
+        drop_kept_blocks()
+        _lib = previous
 
 
 # Caches of caller-kept counter / ticket blocks (ops._scatter_counters, ops._zeroed_words, ops._pose_scratch, FusedAdam's

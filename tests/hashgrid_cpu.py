@@ -14,6 +14,8 @@ and only an explicit fmaf is one.
 Inputs stay clear of fp32 underflow (tests/test_hashgrid_fp64_cpu.py asserts that the smallest non-zero product is above
 2^-100), so no bound needs an absolute floor.
 """
+import dataclasses
+import re
 from fractions import Fraction
 
 import numpy as np
@@ -23,12 +25,98 @@ U64 = 2.0 ** -53                 # ... of float64
 _U32 = np.uint64(0xFFFFFFFF)
 P1, P2 = 2654435761, 805459861   # hashgrid.hip P1, P2
 
-# the routed scatter's constants (hashgrid.hip)
-SC_MAX_SLICE = 8192              # MIPSF_SC_MAX_SLICE: a level of up to this many entries is one slice
-SC_SLICE_LOG2 = 13               # MIPSF_SC_SLICE_LOG2: slices of a larger level
-SC_PART = 24576                  # MIPSF_SC_PART: records per work item, hashed level
-SC_PART_DENSE = 8192             # MIPSF_SC_PART_DENSE: ... dense level
-SC_RUN = 4                       # MIPSF_SC_RUN: records merged in registers per thread on a dense level
+
+
+@dataclasses.dataclass(frozen=True)
+class Build:
+    """The compile-time constants of the routed scatter (hashgrid.hip) that decide what a record, a part and a rounding is.
+    One instance per library build: DEFAULT is the shipped library, BUILDS[name] the variant `name` of csrc/variants.mk (the
+    defaults with that variant's -D overrides; tests/test_hashgrid_fp64_cpu.py asserts that the two lists agree)."""
+    max_slice: int = 8192            # MIPSF_SC_MAX_SLICE: a level of up to this many entries is one slice
+    slice_log2: int = 13             # MIPSF_SC_SLICE_LOG2: slices of a larger level
+    part: int = 24576                # MIPSF_SC_PART: records per work item, hashed level
+    part_dense: int = 8192           # MIPSF_SC_PART_DENSE: ... dense level
+    run: int = 4                     # MIPSF_SC_RUN: records merged in registers per thread on a dense level
+    masked_max_m: int = 1 << 24      # MIPSF_SC_MASKED_MAX_M: up to this many samples a record carries its corner mask
+    rt_block: int = 512              # MIPSF_RT_BLOCK: threads of a routing workgroup, SC_ROUTE_UNR = 4 samples each
+    rt_levels: int = 1               # MIPSF_RT_LEVELS: levels routed by one workgroup
+    stage_cap_words: int = 0         # MIPSF_SC_STAGE_CAP: records a routing workgroup stages per level (0: 10 * rt_block)
+    skip_zero: int = 1               # MIPSF_SC_SKIP_ZERO: 0 = dead pairs get records too
+    # switches that change how the kernels work and nothing a record, a part or a rounding count depends on
+    route_fast: int = 1              # MIPSF_SC_ROUTE_FAST
+    planar: int = 1                  # MIPSF_SC_PLANAR
+    stage: int = 1                   # MIPSF_SC_STAGE
+    agg_max: int = 1                 # MIPSF_SC_AGG_MAX
+    publish_wt: int = 1              # MIPSF_SC_PUBLISH_WT
+
+    @property
+    def stage_cap(self):
+        return self.stage_cap_words or 10 * self.rt_block
+
+    @property
+    def route_chunk(self):
+        """consecutive samples of one routing workgroup (RT_BLOCK * SC_ROUTE_UNR)"""
+        return 4 * self.rt_block
+
+    def live(self, dout, n_levels=None):
+        """[M,L] bool, the (sample, level) pairs scatter_route_kernel gives records, or None for all of them.
+        MIPSF_SC_SKIP_ZERO = 0: the routing kernel is not shown dout at all.  MIPSF_RT_LEVELS > 1: a workgroup routes the
+        levels group, group + G, group + 2 G, ... (G = ceil(L / RT_LEVELS)) from ONE liveness mask -- a sample is live when
+        its gradient is non-zero on any of them -- so a pair that is dead by itself gets records through its group (they add
+        exact zeros: the part counts move, the sums do not)."""
+        if not self.skip_zero:
+            return None
+        live = live_pairs(dout)
+        if self.rt_levels > 1:
+            L = live.shape[1]
+            G = (L + self.rt_levels - 1) // self.rt_levels
+            for g in range(G):
+                live[:, g::G] = live[:, g::G].any(1, keepdims=True)
+        return live
+
+
+# macro of csrc/variants.mk -> field of Build
+BUILD_MACROS = {"MIPSF_SC_MAX_SLICE": "max_slice", "MIPSF_SC_SLICE_LOG2": "slice_log2", "MIPSF_SC_PART": "part",
+                "MIPSF_SC_PART_DENSE": "part_dense", "MIPSF_SC_RUN": "run", "MIPSF_SC_MASKED_MAX_M": "masked_max_m",
+                "MIPSF_RT_BLOCK": "rt_block", "MIPSF_RT_LEVELS": "rt_levels", "MIPSF_SC_STAGE_CAP": "stage_cap_words",
+                "MIPSF_SC_SKIP_ZERO": "skip_zero", "MIPSF_SC_ROUTE_FAST": "route_fast", "MIPSF_SC_PLANAR": "planar",
+                "MIPSF_SC_STAGE": "stage", "MIPSF_SC_AGG_MAX": "agg_max", "MIPSF_SC_PUBLISH_WT": "publish_wt"}
+DEFAULT = Build()
+BUILDS = {
+    "maskless": Build(masked_max_m=1024),
+    "small": Build(masked_max_m=1024, stage_cap_words=512, part=2048, part_dense=1024),
+    "slice10": Build(max_slice=1024, slice_log2=10),
+    "general": Build(route_fast=0),
+    "rt2": Build(rt_levels=2),
+    "rt4": Build(rt_levels=4),
+    "interleaved": Build(planar=0),
+    "nostage": Build(stage=0),
+    "agg8": Build(agg_max=8),
+    "fence": Build(publish_wt=0),
+    "keepzero": Build(skip_zero=0),
+    "run1": Build(run=1),
+    "rtb256": Build(rt_block=256),
+}
+# the shipped library's, under the names the kernels use
+SC_MAX_SLICE, SC_SLICE_LOG2, SC_PART, SC_PART_DENSE, SC_RUN = (DEFAULT.max_slice, DEFAULT.slice_log2, DEFAULT.part,
+                                                               DEFAULT.part_dense, DEFAULT.run)
+SC_MAX_NS, SC_MAX_BINS = 512, 8192     # hashgrid.hip: slices a level, bins a table (check_plan refuses more)
+
+
+def parse_variants(text):
+    """csrc/variants.mk -> {name: (unit, {macro: value})}"""
+    names = re.findall(r"^VARIANTS\s*\+=\s*(\w+)\s*$", text, re.M)
+    out = {}
+    for name in names:
+        unit = re.search(rf"^{name}_UNIT\s*=\s*(\w+)\s*$", text, re.M).group(1)
+        flags = re.search(rf"^{name}_FLAGS\s*=\s*(.*)$", text, re.M).group(1).split()
+        macros = {}
+        for f in flags:
+            m = re.fullmatch(r"-D(\w+)=(\d+)", f)
+            assert m, f"variant {name}: flag {f} is not -DNAME=<integer>"
+            macros[m.group(1)] = int(m.group(2))
+        out[name] = (unit, macros)
+    return out
 
 
 def gamma(k):
@@ -54,10 +142,16 @@ K_DX = (K_DXL
 K_SCATTER = (K_WEIGHT
              + 1   # scatter_item: `wgt * gy.x`
              + 1)  # scatter_item: `(float)a.x` -- the fp64 slice sum leaves as fp32 (to dparams or to a partial slice)
-K_SCATTER_DENSE_RUN = SC_RUN - 1   # scatter_item, dense level: `sum[c][0] = sum[c][0] + wgt * gy.x`, up to SC_RUN records per run,
-#                                    the first onto 0.0f
-# + (parts - 1): hashgrid_scatter_reduce_kernel `a.x += v[k].x` over the bin's parts, the first onto 0.f; `cur.x += a.x` is exact
-#   onto the zero a fresh dparams holds.  An accumulate into non-zero dparams rounds the RESULT once more: + u |value|.
+
+
+def K_SCATTER_DENSE_RUN(build=DEFAULT):
+    """scatter_item, dense level: `sum[c][0] = sum[c][0] + wgt * gy.x`, up to SC_RUN records per run, the first onto 0.0f"""
+    return build.run - 1
+
+
+# + (parts - 1): fold_entry `a.x += v[k].x` over the bin's parts in part order, eight loads at a time (the slots past the last part
+#   hold 0.f: exact), the first onto 0.f; `cur.x += a.x` is exact onto the zero a fresh dparams holds.  An accumulate into
+#   non-zero dparams rounds the RESULT once more: + u |value|.
 
 
 class Levels:
@@ -246,17 +340,24 @@ def bound_dx(R, L):
     return (gamma(K_DX) + (6 + 5 + 3 + L) * U64) * R["A_dx"]
 
 
-def scatter_plan(levels, R, live=None):
+def _slices(levels, level, build):
+    """-> (slices of the level, the shift that takes an entry index to its slice)"""
+    size = levels.size(level)
+    if size <= build.max_slice:
+        return 1, 31
+    return (size + (1 << build.slice_log2) - 1) >> build.slice_log2, build.slice_log2
+
+
+def scatter_plan(levels, R, live=None, build=DEFAULT):
     """The records and parts of every bin of the routed scatter (hashgrid.hip make_plan, scatter_route_kernel, part_of).
-    live [M,L] bool: the (sample, level) pairs that get records (None: all, as after mipsf_hashgrid_route, which sees no dout).
+    live [M,L] bool: the (sample, level) pairs that get records (None: all, as after mipsf_hashgrid_route, which sees no dout);
+    for a build other than the shipped one it is build.live(dout).
     A record is a sample with at least one corner in the bin's slice.
     -> list per level of dict(dense, shift, records [slices], parts [slices])"""
     plan = []
     for level in range(levels.n_levels):
         size = levels.size(level)
-        one = size <= SC_MAX_SLICE
-        ns = 1 if one else (size + (1 << SC_SLICE_LOG2) - 1) >> SC_SLICE_LOG2
-        shift = 31 if one else SC_SLICE_LOG2
+        ns, shift = _slices(levels, level, build)
         idx = R["idx"][:, level]
         if live is not None:
             idx = idx[live[:, level]]
@@ -264,9 +365,25 @@ def scatter_plan(levels, R, live=None):
         key = np.unique(np.arange(sl.shape[0])[:, None] * ns + sl)         # distinct (sample, slice)
         records = np.bincount(key % ns, minlength=ns)
         dense = not level_is_hashed(levels.res[level], size)
-        part = SC_PART_DENSE if dense else SC_PART
+        part = build.part_dense if dense else build.part
         plan.append(dict(dense=dense, shift=shift, records=records, parts=(records + part - 1) // part))
     return plan
+
+
+def route_chunk_records(levels, R, live=None, build=DEFAULT):
+    """[chunks, L]: the records one routing workgroup makes on one level (scatter_route_kernel: a workgroup takes
+    RT_BLOCK * SC_ROUTE_UNR consecutive samples; the records past MIPSF_SC_STAGE_CAP leave by the lane-per-record store)."""
+    M = R["idx"].shape[0]
+    chunk = build.route_chunk
+    n_chunks = (M + chunk - 1) // chunk
+    out = np.zeros((n_chunks, levels.n_levels), np.int64)
+    for level in range(levels.n_levels):
+        ns, shift = _slices(levels, level, build)
+        sample = np.arange(M) if live is None else np.flatnonzero(live[:, level])
+        sl = R["idx"][sample, level] >> shift
+        key = np.unique(sample[:, None] * ns + sl)                         # distinct (sample, slice)
+        out[:, level] = np.bincount((key // ns) // chunk, minlength=n_chunks)
+    return out
 
 
 def live_pairs(dout):
@@ -274,15 +391,21 @@ def live_pairs(dout):
     return ~((dout[..., 0] == 0) & (dout[..., 1] == 0))
 
 
-def bound_dp(levels, R, plan):
-    """[E,2]: the routed scatter into a dparams that is zero on entry"""
+def roundings_dp(levels, R, plan, build=DEFAULT):
+    """[E]: fp32 roundings on the longest path of every entry's sum, routed scatter into a dparams that is zero on entry"""
     entries = R["entries"]
     level = np.searchsorted(np.asarray(levels.offsets), entries, side="right") - 1
     k = np.empty(entries.size)
     for l in range(levels.n_levels):
         m = level == l
         parts = plan[l]["parts"][(entries[m] - levels.offsets[l]) >> plan[l]["shift"]]
-        k[m] = K_SCATTER + (K_SCATTER_DENSE_RUN if plan[l]["dense"] else 0) + np.maximum(parts, 1) - 1
+        k[m] = K_SCATTER + (K_SCATTER_DENSE_RUN(build) if plan[l]["dense"] else 0) + np.maximum(parts, 1) - 1
+    return k
+
+
+def bound_dp(levels, R, plan, build=DEFAULT):
+    """[E,2]: the routed scatter into a dparams that is zero on entry; plan = scatter_plan(..., build)"""
+    k = roundings_dp(levels, R, plan, build)
     # float64 side: the weight (6), the product, the reference's n-term sum; the kernel's fp64 LDS atomics: n more
     return (gamma(k) + (7 + 2 * R["n_dp"]) * U64)[:, None] * R["A_dp"]
 
@@ -385,3 +508,19 @@ SCATTER_CASES = [
     ("t14_m1", 14, 1, 0.3, "one sample"),
 ]
 FWD_M = [1, 63, 64, 65, 255, 256, 257, 9000]
+# the two sides of the `maskless` variant's limit (MIPSF_SC_MASKED_MAX_M = 1024): 1024 samples still carry corner masks
+MASK_EDGE_CASES = [
+    ("t14_m1024", 14, 1024, 0.3, "the last batch size whose records carry the corner mask"),
+    ("t14_m1025", 14, 1025, 0.3, "the first batch size whose records are bare sample indices"),
+]
+# the cases every variant library of csrc/variants.mk runs (tests/test_gpu_hashgrid_variants.py), and what
+# tests/test_hashgrid_fp64_cpu.py shows them to reach
+VARIANT_CASES = {
+    "maskless": ["t14_m9000", "t10_m25000", "t19_m3000", "hand_m3000", "t14_m1024", "t14_m1025"],
+    "small": ["t14_m25000", "t10_m25000"],
+    "slice10": ["t19_m3000", "hand_m3000", "t14_m9000"],
+    **{v: ["t14_m9000", "t19_m3000", "hand_m3000", "t14_m1"] for v in ("general", "nostage", "agg8", "interleaved", "rtb256")},
+    **{v: ["t14_m9000", "t19_m3000"] for v in ("rt2", "rt4", "keepzero")},
+    **{v: ["t14_m25000", "t10_m25000"] for v in ("fence", "run1")},
+}
+CASES_BY_NAME = {c[0]: c for c in SCATTER_CASES + MASK_EDGE_CASES}

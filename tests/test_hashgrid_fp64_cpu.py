@@ -4,7 +4,11 @@ recorded vectors before tests/test_gpu_hashgrid_fp64.py holds the kernels to it:
   * the oracle (an honest fp32 implementation in the kernel's operation order: forward, per-level Jacobian, per-level and summed dx)
     and the recorded features stay inside the bounds;
   * the inputs the GPU cases use hold every planted kind, hit every addressing mode, give the part counts the cases are there
-    for, have no unresolved double-rounding case and stay clear of underflow."""
+    for, have no unresolved double-rounding case and stay clear of underflow;
+  * the variant libraries of csrc/variants.mk (tests/test_gpu_hashgrid_variants.py) exist, speak the ABI, are compiled with the
+    constants the restatement takes for them (H.BUILDS), and their cases reach what each variant is there for: records whose
+    corner membership the accumulate kernel recomputes, bins in more than 8 and 16 parts, records past the staging capacity (in
+    the shipped build too), 512 slices a level, pairs that are live only through their routing group."""
 import dataclasses
 import math
 
@@ -199,7 +203,7 @@ def test_part_counts_of_the_scatter_cases(name, table, M, dead, why):
 
 
 @pytest.mark.parametrize("table,M,dead", [(t, m, 0.3) for t in (14, "hand") for m in H.FWD_M]
-                         + [(c[1], c[2], c[3]) for c in H.SCATTER_CASES])
+                         + [(c[1], c[2], c[3]) for c in H.SCATTER_CASES + H.MASK_EDGE_CASES])
 def test_no_unresolved_rounding_and_no_underflow(table, M, dead):
     R = case(table, M, dead)[-1]
     assert R["fma"][1] == 0, f"{R['fma'][1]} positions whose single rounding could not be settled"
@@ -237,3 +241,144 @@ def test_fma32_rounds_once():
         near = np.float32(float(exact))
         cands = [np.nextafter(near, np.float32(-np.inf)), near, np.nextafter(near, np.float32(np.inf))]
         assert abs(Fraction(float(got)) - exact) == min(abs(Fraction(float(c)) - exact) for c in cands)
+
+
+# ------------------------------------------------------------------- the variant libraries: the cases reach what they are there for
+# (tests/test_gpu_hashgrid_variants.py runs them; here on the restatement alone)
+def named(name):
+    _, table, M, dead, _ = H.CASES_BY_NAME[name]
+    return case(table, M, dead)
+
+
+def variant_plan(variant, name):
+    meta, lv, x, params, dout, kinds, R = named(name)
+    build = H.BUILDS[variant]
+    live = build.live(dout)
+    return lv, R, dout, build, live, H.scatter_plan(lv, R, live, build)
+
+
+def test_variant_records_are_the_makefiles():
+    """H.BUILDS (the constants the restatement takes) and csrc/variants.mk (the flags the libraries are compiled with) agree"""
+    import os
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    with open(os.path.join(root, "mipsfusion_amd", "csrc", "variants.mk")) as f:
+        listed = H.parse_variants(f.read())
+    assert list(listed) == list(H.BUILDS) and set(H.VARIANT_CASES) == set(H.BUILDS)
+    for name, (unit, macros) in listed.items():
+        assert unit == "hashgrid" and macros and set(macros) <= set(H.BUILD_MACROS), f"{name}: {macros}"
+        want = dataclasses.replace(H.DEFAULT, **{H.BUILD_MACROS[m]: v for m, v in macros.items()})
+        assert H.BUILDS[name] == want and want != H.DEFAULT, f"{name}: {H.BUILDS[name]} against {macros}"
+    # the shipped constants are the sources' defaults
+    with open(os.path.join(root, "mipsfusion_amd", "csrc", "hashgrid.hip")) as f:
+        src = f.read()
+    import re
+    for macro, field in H.BUILD_MACROS.items():
+        m = re.search(rf"#ifndef {macro}\n#define {macro} ([^\n/]*)", src)
+        assert m, macro
+        text = m.group(1).strip().replace("u", "")
+        value = {"(1 << 24)": 1 << 24, "(10 * RT_BLOCK)": 0}.get(text)
+        assert (int(text) if value is None else value) == getattr(H.DEFAULT, field), f"{macro}: {text}"
+    assert H.DEFAULT.stage_cap == 10 * H.DEFAULT.rt_block and H.BUILDS["rtb256"].stage_cap == 2560 and H.BUILDS["small"].stage_cap == 512
+
+
+@pytest.mark.parametrize("variant", list(H.BUILDS))
+def test_variant_library_is_built_and_speaks_abi_2(variant):
+    from mipsfusion_amd import _lib
+    assert _lib.load(_lib.variant_path(variant)).mipsf_abi_version() == 2
+
+
+@pytest.mark.parametrize("name", H.VARIANT_CASES["maskless"])
+def test_maskless_cases_leave_membership_to_the_accumulate_kernel(name):
+    """Beyond MIPSF_SC_MASKED_MAX_M a record is the bare sample index and scatter_item recomputes which of the 8 corners are in
+    its slice.  That decides something where a sample has corners in two slices of a hashed level: it then has more records
+    than one, and each must take only its own corners."""
+    lv, R, dout, build, live, plan = variant_plan("maskless", name)
+    M = dout.shape[0]
+    if name == "t14_m1024":
+        assert M == build.masked_max_m, "the last size that still carries masks"
+        return
+    assert M > build.masked_max_m
+    split = [l for l, p in enumerate(plan) if not p["dense"] and p["records"].sum() > live[:, l].sum()]
+    if name == "t10_m25000":
+        # a 2^10 table has no level of more than one slice, so no sample can have two records on a level: what this case adds
+        # is the mask-less record in bins of several parts, all 8 corners members (the pair walk with a full mask)
+        assert not split and all(len(p["parts"]) == 1 and not p["dense"] and p["parts"][0] == 2 for p in plan)
+        return
+    assert split, "no hashed level where a sample has corners in two slices"
+    if name == "hand_m3000":
+        assert H.HAND_LEVEL in split and H.level_mode(lv.res[H.HAND_LEVEL], lv.size(H.HAND_LEVEL)) == 2
+    if name == "t14_m1025":
+        assert M == build.masked_max_m + 1
+
+
+def test_small_cases_fold_many_parts_and_overflow_the_stage():
+    build = H.BUILDS["small"]
+    lv, R, dout, _, live, plan = variant_plan("small", "t14_m25000")
+    assert max(int(p["parts"].max()) for p in plan if p["dense"]) > 16, "a dense bin in more than 16 parts (fold_entry: three rounds of 8)"
+    lv10, R10, dout10, _, live10, plan10 = variant_plan("small", "t10_m25000")
+    assert all(not p["dense"] and int(p["parts"].min()) > 8 for p in plan10), "every hashed bin in more than 8 parts"
+    for lv_, R_, live_ in ((lv, R, live), (lv10, R10, live10)):
+        rc = H.route_chunk_records(lv_, R_, live_, build)
+        assert rc.shape[0] == (25000 + 2047) // 2048 and rc.max() > build.stage_cap
+        assert np.maximum(rc - build.stage_cap, 0).sum() > rc.sum() // 2, "most records leave by the lane-per-record store"
+    assert all(M > build.masked_max_m for M in (dout.shape[0], dout10.shape[0]))
+
+
+def test_shipped_constants_reach_the_overflow_store_on_t19_m3000():
+    meta, lv, x, params, dout, kinds, R = named("t19_m3000")
+    rc = H.route_chunk_records(lv, R, H.DEFAULT.live(dout), H.DEFAULT)
+    assert rc.shape == (2, 16) and H.DEFAULT.stage_cap == 5120
+    assert rc[0].max() > H.DEFAULT.stage_cap, f"the first 2048 samples make at most {rc[0].max()} records a level"
+    assert rc[0].min() < H.DEFAULT.stage_cap, "and a level that stays inside the stage"
+
+
+def test_slice10_case_has_512_slices_a_level():
+    lv, R, dout, build, live, plan = variant_plan("slice10", "t19_m3000")
+    ns = [len(p["parts"]) for p in plan]
+    assert max(ns) == H.SC_MAX_NS == 512 and ns.count(512) >= 1
+    assert sum(ns) <= H.SC_MAX_BINS and sum(ns) <= 0xFFFF
+    assert all(p["records"][-1] > 0 for p, n in zip(plan, ns) if n == 512), "the 512th slice of every such level has records"
+    # dense levels cut into slices thinner than a cell's index span (res^2 + res + 1): the fast dense grouping declines them
+    assert any(p["dense"] and len(p["parts"]) > 1 and lv.res[l] ** 2 + lv.res[l] + 1 > 1 << build.slice_log2 for l, p in enumerate(plan))
+    for name in H.VARIANT_CASES["slice10"]:
+        assert sum(len(p["parts"]) for p in variant_plan("slice10", name)[-1]) <= H.SC_MAX_BINS
+
+
+@pytest.mark.parametrize("variant", ["rt2", "rt4"])
+@pytest.mark.parametrize("name", H.VARIANT_CASES["rt2"])
+def test_routing_groups_give_dead_pairs_records(variant, name):
+    lv, R, dout, build, live, plan = variant_plan(variant, name)
+    alone = H.live_pairs(dout)
+    assert (live | ~alone).all() and (live & ~alone).sum() > 0, "no pair that is dead by itself and live through its group"
+    G = 16 // build.rt_levels
+    s, l = np.argwhere(live & ~alone)[0]
+    assert alone[s, l % G::G].any() and not alone[s, l]
+    assert (~live).sum() > 0, "and pairs that stay dead: the whole group is"
+    shipped = H.scatter_plan(lv, R, alone)
+    assert any((a["records"] != b["records"]).any() for a, b in zip(shipped, plan)), "the two plans do not differ"
+    assert all((a["records"] <= b["records"]).all() for a, b in zip(shipped, plan))
+
+
+def test_keepzero_plan_is_the_routed_ahead_plan():
+    lv, R, dout, build, live, plan = variant_plan("keepzero", "t14_m9000")
+    assert live is None
+    ahead = H.scatter_plan(lv, R, None)
+    assert all(np.array_equal(a["records"], b["records"]) for a, b in zip(ahead, plan))
+
+
+@pytest.mark.parametrize("name", H.VARIANT_CASES["run1"])
+def test_run1_bound_is_the_defaults_minus_the_run_merge(name):
+    lv, R, dout, build, live, plan = variant_plan("run1", name)
+    k1 = H.roundings_dp(lv, R, plan, build)
+    k4 = H.roundings_dp(lv, R, H.scatter_plan(lv, R, H.live_pairs(dout)), H.DEFAULT)
+    level = np.searchsorted(np.asarray(lv.offsets), R["entries"], side="right") - 1
+    dense = np.array([p["dense"] for p in plan])[level]
+    assert np.array_equal(k4[dense] - k1[dense], np.full(dense.sum(), H.SC_RUN - 1.0)) and np.array_equal(k4[~dense], k1[~dense])
+    if name == "t14_m25000":
+        assert dense.any()
+    assert (H.bound_dp(lv, R, plan, build) <= H.bound_dp(lv, R, plan, H.DEFAULT)).all()
+
+
+@pytest.mark.parametrize("variant,name", [(v, n) for v in ("fence", "run1") for n in H.VARIANT_CASES[v]])
+def test_fence_and_run1_cases_have_split_bins(variant, name):
+    assert max(int(p["parts"].max()) for p in variant_plan(variant, name)[-1]) >= 2

@@ -6,7 +6,7 @@ cd "$(dirname "$0")/../.."
 NAME=$1; shift
 SRC=mipsfusion_amd/csrc
 make -s -C $SRC >/dev/null
-ALL="capi hashgrid elementwise render decoder decoder16 wgrad16 pose ro"
+ALL=$(make -s -C $SRC units)       # every unit of the library: the experiment keeps the whole C ABI
 UNITS=${UNITS:-$ALL}
 OBJS=""
 for u in $ALL; do
