@@ -422,14 +422,22 @@ def worst_ratio(got, want, bound):
 
 
 # ------------------------------------------------------------------------------------------------------------------- the inputs
-def build_inputs(levels, M, seed, dead_share=0.3):
+X_LO, X_HI = -1.5, 2.5           # the range real rays reach (decoder_cpu.X_LO, X_HI; this module imports no torch)
+
+
+def build_inputs(levels, M, seed, dead_share=0.3, outside=False):
     """-> x [M,3], params [2 * entries], dout [M,L,2] (fp32), kinds {name: sample indices planted}.
-    dead_share: about this share of the (sample, level) pairs carries a zero gradient (ray tails, whole samples, single pairs)."""
+    dead_share: about this share of the (sample, level) pairs carries a zero gradient (ray tails, whole samples, single pairs).
+    outside: x is drawn over [X_LO, X_HI]^3, as the samples of real rays are -- three points in four lie outside the unit box, on
+    negative cells and on cells past the level's resolution, whose corners wrap (the planted kinds stay as they are)."""
     rng = np.random.default_rng(seed)
     L = levels.n_levels
     sc = levels.scales.astype(np.float64)
     x = rng.random((M, 3)).astype(np.float32)
-    x = np.clip(x, np.float32(1e-3), np.float32(1 - 1e-3))                  # the interior
+    if outside:
+        x = (np.float32(X_LO) + np.float32(X_HI - X_LO) * x).astype(np.float32)
+    else:
+        x = np.clip(x, np.float32(1e-3), np.float32(1 - 1e-3))              # the interior
     kinds = {}
     taken = np.zeros(M, bool)
     if M >= 128:                                                            # 64 consecutive samples of one ray
@@ -508,6 +516,9 @@ SCATTER_CASES = [
     ("t14_m1", 14, 1, 0.3, "one sample"),
 ]
 FWD_M = [1, 63, 64, 65, 255, 256, 257, 9000]
+# points over [X_LO, X_HI]^3 (build_inputs(outside=True)): (table, M) -- a 2^16 and a 2^19 table, and the hand-made meta for the
+# % addressing; every kernel form runs them in both layouts, under the same derived bounds
+OUTSIDE_CASES = [(16, 257), (19, 130), ("hand", 257)]
 # the two sides of the `maskless` variant's limit (MIPSF_SC_MASKED_MAX_M = 1024): 1024 samples still carry corner masks
 MASK_EDGE_CASES = [
     ("t14_m1024", 14, 1024, 0.3, "the last batch size whose records carry the corner mask"),

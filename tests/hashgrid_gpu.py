@@ -31,11 +31,11 @@ _CASES = {}
 
 
 class Case:
-    def __init__(self, table, M, dead, dev):
+    def __init__(self, table, M, dead, dev, outside=False):
         self.meta = gmeta(table)
         self.lv = H.Levels(self.meta)
         self.M = M
-        self.x, self.params, self.dout, self.kinds = H.build_inputs(self.lv, M, M + 7, dead)
+        self.x, self.params, self.dout, self.kinds = H.build_inputs(self.lv, M, M + 7, dead, outside)
         self.R = H.reference(self.lv, self.x, self.params, self.dout)
         self.xg, self.pg = torch.from_numpy(self.x).to(dev), torch.from_numpy(self.params).to(dev)
 
@@ -45,10 +45,10 @@ class Case:
         return torch.from_numpy(d).to(self.xg.device)
 
 
-def case(table, M, dead, dev):
-    key = (table, M, dead)
+def case(table, M, dead, dev, outside=False):
+    key = (table, M, dead, outside)
     if key not in _CASES:
-        _CASES[key] = Case(table, M, dead, dev)
+        _CASES[key] = Case(table, M, dead, dev, outside)
     return _CASES[key]
 
 

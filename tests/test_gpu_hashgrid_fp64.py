@@ -133,6 +133,38 @@ def test_routed_scatter_routed_ahead(dev, name, table, M, dead, why):
     held_dparams("scatter, routed ahead", name, c, dp, R["dp"], b)
 
 
+# ----------------------------------------------------------------------------------------------------- points outside the unit box
+@pytest.mark.parametrize("lname,layout", LAYOUTS)
+@pytest.mark.parametrize("table,M", H.OUTSIDE_CASES)
+def test_points_outside_the_unit_box(dev, table, M, lname, layout):
+    """x over [-1.5, 2.5]^3, where real rays put their samples: negative cells, wrapped corners, all three addressing modes
+    (tests/test_hashgrid_fp64_cpu.py asserts that they occur) -- forward, Jacobian, d x by both paths and the routed scatter under
+    the same derived bounds as the interior points"""
+    c = case(table, M, 0.3, dev, outside=True)
+    R = c.R
+    tag = f"outside {table} M={M} {lname}"
+    assert np.array_equal(ops.hashgrid_indices(c.xg, c.meta).cpu().numpy().astype(np.int64), R["idx"])
+
+    def std(y):
+        y = y.cpu().numpy()
+        return y.reshape(M, 16, 2) if layout == FEAT_AOS else y.transpose(1, 0, 2)
+    held("forward", tag, std(ops.hashgrid_fwd(c.xg, c.pg, c.meta, layout)), R["y"], H.bound_y(R))
+    yj, jac = ops.hashgrid_fwd(c.xg, c.pg, c.meta, layout, with_jac=True)
+    held("forward (with the Jacobian)", tag, std(yj), R["y"], H.bound_y(R))
+    held("Jacobian", tag, jac.cpu().numpy().transpose(2, 0, 1, 3), R["J"], H.bound_J(R))
+    dg = c.dout_dev(layout)
+    for form, run in (("dx (gather)", lambda dx: gather_dx(c, layout, dg, dx)),
+                      ("dx (saved Jacobian)", lambda dx: ops.hashgrid_dx_from_jac(jac, dg, dx, c.meta, layout))):
+        dx = torch.zeros(M, 3, device=dev)
+        run(dx)
+        held(form, tag, dx, R["dx"], H.bound_dx(R, 16))
+    b = H.bound_dp(c.lv, R, H.scatter_plan(c.lv, R, H.live_pairs(c.dout)))
+    for fresh in (False, True):
+        dp = torch.zeros_like(c.pg)
+        ops.hashgrid_bwd(c.xg, c.pg, dg, dp, c.meta, layout, None, dparams_zero=fresh)
+        held_dparams("scatter" + (", dparams_zero" if fresh else ""), tag, c, dp, R["dp"], b)
+
+
 @pytest.mark.parametrize("lname,layout", LAYOUTS)
 def test_all_dead_gradient_writes_nothing(dev, lname, layout):
     all_dead_gradient_writes_nothing(case(14, 9000, 0.01, dev), layout)

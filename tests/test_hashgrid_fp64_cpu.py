@@ -117,6 +117,36 @@ def test_oracle_per_level_jacobian_and_dx_inside_the_bounds(table):
     print(f"\n  oracle / bound | {table} | Jacobian {worst_j:.3f} | per-level dx {worst_d:.3f}", end="")
 
 
+def test_outside_cases_meet_what_the_bound_derivation_needs():
+    """build_inputs(outside=True): points over [-1.5, 2.5]^3.  The bounds are derived for ANY cell the kernel's own fmaf and floor give,
+    on the conditions asserted here: no unresolved fma, every |floor| below 2^31 (both counted in R["fma"][1]), no product near fp32's
+    underflow.  And the cases reach what they are there for: negative cells, cells past the resolution, all three addressing modes,
+    and an honest fp32 implementation (the oracle) inside the bounds out there."""
+    from . import decoder_cpu
+    assert (H.X_LO, H.X_HI) == (decoder_cpu.X_LO, decoder_cpu.X_HI)
+    modes = set()
+    for table, M in H.OUTSIDE_CASES:
+        meta = ometa(table)
+        lv = H.Levels(meta)
+        x, params, dout, kinds = H.build_inputs(lv, M, M + 7, 0.3, outside=True)
+        inside_x, _, _, _ = H.build_inputs(lv, M, M + 7, 0.3)
+        assert x.min() < -1.3 and x.max() > 2.3 and ((x < 0) | (x > 1)).any(1).mean() > 0.4 and inside_x.shape == x.shape
+        R = H.reference(lv, x, params, dout)
+        assert R["fma"][1] == 0, f"{R['fma'][1]} unresolved fma or cells beyond 2^31"
+        assert R["min_product"] > 2.0 ** -100
+        cells = R["c"].astype(np.int64)
+        assert (cells >= 2 ** 31).any(), "negative cells (uint32 values above 2^31)"
+        assert ((cells < 2 ** 31) & (cells >= np.asarray(lv.res)[None, :, None])).any(), "cells past the level's resolution"
+        modes |= R["modes"]
+        assert np.array_equal(R["idx"], tcnn_cpu.hashgrid_indices(T(x), meta).numpy())
+        y = tcnn_cpu.hashgrid_forward(T(x), T(params), meta).numpy().reshape(M, 16, 2)
+        ry = inside(y, R["y"], H.bound_y(R), "oracle forward, outside")
+        _, dx = tcnn_cpu.hashgrid_backward(T(x), T(params), T(dout.reshape(M, 32)), meta)
+        rx = inside(dx.numpy(), R["dx"], H.bound_dx(R, 16), "oracle summed dx, outside")
+        print(f"\n  oracle / bound | outside {table} M={M} | forward {ry:.3f} | summed dx {rx:.3f}", end="")
+    assert modes == {0, 1, 2}
+
+
 @pytest.mark.parametrize("table,M", [(14, 257), (14, 9000), ("hand", 3000), (10, 25000), (19, 3000)])
 def test_every_planted_kind_is_present(table, M):
     dead = 0.01 if M in (9000, 25000) else 0.3
